@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Train-throughput benchmark of the MI355X DeepSpeech2 hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one full training pass over one minibatch of synthetic 16 kHz clips already resident in HBM:
@@ -456,6 +456,89 @@ def _fallbacks():
     return int(ops.fallback_count)
 
 
+DUMP_SAMPLE = 1 << 20               # --dump-outputs: elements drawn from each flat parameter-sized buffer
+DUMP_SAMPLE_SEED = 20181015
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_REPLAY_STEPS = 3               # minibatches replayed from the seeded state; the dump is taken after the last one
+
+
+def training_state(model, trainer):
+    """A device copy of everything a training step reads besides its minibatch: the flat parameters, the momentum buffer
+    and whether it is still unset, and every BatchNorm's running statistics."""
+    if model._flat_p.is_cuda:
+        torch.cuda.synchronize(model._flat_p.device)
+    bns = [m for m in model.modules() if hasattr(m, 'num_batches_tracked')]
+    return {'params': model._flat_p.detach().clone(),
+            'momentum': None if trainer._buf is None else trainer._buf.detach().clone(),
+            'first': trainer._first,
+            'bn': [(m.running_mean.detach().clone(), m.running_var.detach().clone(), m.num_batches_tracked.detach().clone())
+                   for m in bns]}
+
+
+def restore_training_state(model, trainer, state):
+    """Put back what ``training_state`` copied (the trainer's buffers stay the same tensors)."""
+    bns = [m for m in model.modules() if hasattr(m, 'num_batches_tracked')]
+    with torch.no_grad():
+        model._flat_p.copy_(state['params'])
+        if state['momentum'] is not None:
+            trainer._buf.copy_(state['momentum'])
+        for m, (mean, var, n) in zip(bns, state['bn']):
+            m.running_mean.copy_(mean)
+            m.running_var.copy_(var)
+            m.num_batches_tracked.copy_(n)
+    trainer._first = state['first']
+    if model._flat_p.is_cuda:
+        torch.cuda.synchronize(model._flat_p.device)
+
+
+def dump_outputs(out_dir, model, trainer, loss):
+    """``--dump-outputs DIR``: what one training step computed, as DIR/<name>.npy, for comparing two builds output for
+    output.  main() replays the LAST ``DUMP_REPLAY_STEPS`` timed minibatches through the timed path's own step function,
+    starting from the run's seeded state (``training_state`` before the warm-up), and dumps after the last of them: that
+    step runs the steady-state update (a momentum buffer built by the steps before it, BatchNorm statistics moved by them)
+    from inputs that are the same in every run.  The weights that enter the real last timed step are not: the backward
+    pass reduces in float with atomics (split-K GEMMs, conv weight gradients, CTC), so two runs differ in the last bit
+    from the first step (gradient norm 2e-9 apart), and this workload's trajectory grows such a difference about 2.2-fold
+    per step, as it does one of weights perturbed by 1e-7: loss 1e-3 apart after 12 steps, 0.15 after 25
+    (profiles/trajectory_divergence.txt, tools/trajectory_divergence.py).  Two runs' dumps of the replayed step agree
+    within 3.5e-6 of each array's scale (profiles/dump_outputs_repeat.txt, tools/compare_dumps.py).
+    A caller of ``Trainer.update`` receives the step's loss and ``last_grad_norm``, and finds the step's results in the
+    model and the optimizer: the parameters after the update, the gradient it applied, the Nesterov momentum and the
+    BatchNorm running statistics.  The flat buffers (38 M parameters of 5 x BiGRU-800, 0.15 GB in fp32) are sampled at
+    one fixed, seeded, sorted set of flat positions (``sample_index.npy``, the same in every run of a model of this size):
+
+      loss, grad_norm        float64 [1]
+      params_sample          float32 [DUMP_SAMPLE]  model._flat_p after the step
+      grad_sample            float32 [DUMP_SAMPLE]  the flat gradient of the step (before clipping)
+      momentum_sample        float32 [DUMP_SAMPLE]  the momentum buffer after the step
+      sample_index           float64 [DUMP_SAMPLE]  the flat positions sampled
+      bn_running_mean / _var float32                every BatchNorm's running statistics, in module order
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    flat = model._flat_p
+    n = int(flat.numel())
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx_t = torch.from_numpy(idx).to(flat.device)
+    bns = [m for m in model.modules() if hasattr(m, 'num_batches_tracked')]
+    arrays = {
+        'loss': np.array([float(loss)], dtype=np.float64),
+        'grad_norm': np.array([float(trainer.last_grad_norm)], dtype=np.float64),
+        'params_sample': flat.detach()[idx_t].float().cpu().numpy(),
+        'grad_sample': model.flat_grad().detach()[idx_t].float().cpu().numpy(),
+        'sample_index': idx.astype(np.float64),
+        'bn_running_mean': torch.cat([m.running_mean.detach().reshape(-1).float().cpu() for m in bns]).numpy(),
+        'bn_running_var': torch.cat([m.running_var.detach().reshape(-1).float().cpu() for m in bns]).numpy(),
+    }
+    if trainer._buf is not None:
+        arrays['momentum_sample'] = trainer._buf.detach()[idx_t].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def note(msg):
     """progress on stderr (stdout carries only the JSON line)"""
     sys.stderr.write('[bench %6.1f s] %s\n' % (time.time() - _T0, msg))
@@ -641,6 +724,10 @@ def main():
                     help="skip the recurrence-floor leg (ablated launches of the fault-injection library, which appear in a "
                          "kernel trace under the product kernels' names)")
     ap.add_argument('--no-f32-leg', action='store_true', help='skip the leg that repeats the steps on the f32-input GEMM kernels')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed legs, replay the last DUMP_REPLAY_STEPS timed minibatches from the seeded starting state and '
+                         'write what the last of them computed as DIR/<name>.npy (dump_outputs); '
+                         'bench_outputs/ in the tree is git-ignored')
     args = ap.parse_args()
     if args.protocol == 'survey':
         args.warmup, args.steps = 20, 100
@@ -712,6 +799,7 @@ def main():
         inputs, pct = front(flat, offs)
         return trainer.update((inputs, labels, pct, lens), defer=True)
 
+    start_state = training_state(model, trainer) if args.dump_outputs else None     # the seeded state (dump_outputs)
     trainer.reserve(int(float(os.environ.get('DS2_BENCH_RESERVE_GB', '8')) * (1 << 30)))   # one allocator block up front (the longest
     # bin needs ~2 GB per step in flight, twice that while the side stream still holds the previous step's buffers)
     note('model built, inputs resident; timing')
@@ -826,6 +914,21 @@ def main():
         cfg3 = {'workload': 'BASELINE configs[3]: 8 x 15 s per GPU (64 x 15 s at 8 GPUs)', 'steps': 8,
                 'frames_per_s': round(8 * 8 * 1501 * world / float(t3[0]), 1),
                 'ms_per_step': round(1e3 * float(t3[0]) / 8, 2)}
+    if args.dump_outputs:
+        # the last DUMP_REPLAY_STEPS timed minibatches through the timed path's step function, from the seeded starting
+        # state (every rank takes part: the step all-reduces); the trained state is put back for the legs below
+        trainer.flush()
+        trained = training_state(model, trainer)
+        restore_training_state(model, trainer, start_state)
+        last = args.warmup + args.steps - 1
+        for i in range(max(0, last + 1 - DUMP_REPLAY_STEPS), last + 1):
+            dump_loss = step_sync(i)
+        if rank == 0:
+            note('outputs of the last of the last %d timed minibatches, replayed from the seeded state, written to %s: %s'
+                 % (DUMP_REPLAY_STEPS, args.dump_outputs,
+                    ', '.join(dump_outputs(args.dump_outputs, model, trainer, dump_loss))))
+        restore_training_state(model, trainer, trained)
+        del trained, start_state
     if rank != 0:
         dist.destroy_process_group()
         return

@@ -15,7 +15,7 @@ same state-dict key names so weights interchange by name
   forward           codes/model.py:182-207  no sequence packing; eval -> softmax
 
 This file is pinned against the reference itself: tests/golden/make_golden.py
-imports /root/reference/codes/model.py in the build container, loads identical
+imports the reference's codes/model.py from a checkout of it, loads identical
 weights into both and commits the reference's outputs as fixtures.
 
 Besides the nn.Module there is ``gru_direction_explicit`` -- the GRU recurrence

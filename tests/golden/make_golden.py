@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""Generate golden fixtures by running the REFERENCE's own model in this container.
+"""Generate golden fixtures by running the REFERENCE's own model.
 
-Run once in the build container (``python tests/golden/make_golden.py``); the
-outputs (``*.npz`` next to this file) are committed, the reference is not.  It
-imports ``/root/reference/codes/model.py`` (which only needs torch) by file
-path, loads the portable weights-from-seed recipe (oracle/model.py
+Run once where a checkout of the reference project exists
+(``DS2_REFERENCE_TREE=<its root> python tests/golden/make_golden.py``); the
+outputs (``*.npz`` and ``*.json`` next to this file) are committed, the reference
+is not.  It imports the reference's ``codes/model.py`` (which only needs torch) by
+file path, loads the portable weights-from-seed recipe (oracle/model.py
 ``seeded_state_dict``) into it and records what the reference computes:
 
   ref_tiny.npz   hidden 32, 2 layers: logits, eval probs, every intermediate,
@@ -39,10 +40,21 @@ path, loads the portable weights-from-seed recipe (oracle/model.py
                  two alternating B=10 minibatches: per-step loss and gradient norm, the final BatchNorm buffers, strided
                  samples of the final weights and of the momentum buffers.
 
+  ref_configs.json
+                 the reference's own scripts/<name>.json for every config this project ships under scripts/.
+  ref_freeze_bn.json
+                 ``freeze_bn_trace`` of the reference model (hidden 16, one layer, seeded weights and input): what
+                 ``freeze_layers`` followed by the update step's ``model.train()`` leaves of the conv block's BatchNorm.
+
 The GPU box regenerates weights and inputs from the same seeds, so only outputs
-are stored.  Nothing here is read at test time except the .npz files.
+are stored.  At test time the tests read the .npz and .json files, and they import
+helpers from this module: the seeded inputs and labels, CASES, and freeze_bn_case /
+freeze_bn_trace, which tests/test_host2_cpu.py runs on the oracle model.  A change
+to those helpers changes the tests and the fixtures' recipe together: regenerate the
+fixtures after it.
 """
 import importlib.util
+import json
 import os
 import sys
 
@@ -57,8 +69,20 @@ sys.path.insert(0, ROOT)
 from oracle.model import seeded_state_dict, swap_fc_en_to_pt_br  # noqa: E402
 
 
+REFERENCE_ENV = 'DS2_REFERENCE_TREE'
+FREEZE_BN_SEED = 1601
+
+
+def reference_root():
+    """Root directory of the reference project's checkout, named by $DS2_REFERENCE_TREE."""
+    root = os.environ.get(REFERENCE_ENV)
+    if not root or not os.path.isfile(os.path.join(root, 'codes', 'model.py')):
+        raise SystemExit('set %s to the root of a checkout of the reference project' % REFERENCE_ENV)
+    return root
+
+
 def load_reference_model_module():
-    path = '/root/reference/codes/model.py'
+    path = os.path.join(reference_root(), 'codes', 'model.py')
     spec = importlib.util.spec_from_file_location('reference_codes_model', path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
@@ -333,14 +357,67 @@ def expected_keys(name):
     return keys
 
 
+def freeze_bn_trace(net, x):
+    """What ``freeze_layers`` does to the conv block's BatchNorm under the reference's update step, on ``net``:
+    ``_freeze_layers`` applies ``batch_norm_eval_mode`` to the layer and turns off its gradients
+    (codes/utils/training_utils.py:52-54,73), ``_update`` calls ``model.train()`` before every forward pass
+    (codes/engine.py:51).  Returns the BatchNorm modules' training flags after each of the two and their statistics around
+    one forward pass of ``x``."""
+    bns = (net.conv[1], net.conv[4])
+
+    def batch_norm_eval_mode(m):
+        if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+            m.eval()
+    net.conv.apply(batch_norm_eval_mode)
+    for p in net.conv.parameters():
+        p.requires_grad = False
+    out = {'training_after_freeze': [bn.training for bn in bns]}
+    net.train()
+    out['training_after_train'] = [bn.training for bn in bns]
+    out['running_mean_before'] = [bn.running_mean.tolist() for bn in bns]
+    net(x)
+    out['num_batches_tracked'] = [int(bn.num_batches_tracked) for bn in bns]
+    out['running_mean'] = [bn.running_mean.tolist() for bn in bns]
+    out['running_var'] = [bn.running_var.tolist() for bn in bns]
+    return out
+
+
+def freeze_bn_case(model_class):
+    """The model and input ``ref_freeze_bn.json`` was recorded with, built from ``model_class`` (the reference's
+    ``DeepSpeech`` or the oracle's)."""
+    net = model_class(rnn_hidden_size=16, num_rnn_layers=1)
+    net.load_state_dict(seeded_state_dict(net, FREEZE_BN_SEED))
+    return net, torch.from_numpy(seeded_inputs(FREEZE_BN_SEED + 1, 2, 60))
+
+
+def shipped_config_names():
+    return sorted(f[:-5] for f in os.listdir(os.path.join(ROOT, 'scripts')) if f.endswith('.json'))
+
+
+def write_host_fixtures(ref):
+    configs = {}
+    for name in shipped_config_names():
+        with open(os.path.join(reference_root(), 'scripts', name + '.json')) as f:
+            configs[name] = json.load(f)
+    with open(os.path.join(HERE, 'ref_configs.json'), 'w') as f:
+        json.dump(configs, f, indent=1, sort_keys=True)
+        f.write('\n')
+    with open(os.path.join(HERE, 'ref_freeze_bn.json'), 'w') as f:
+        json.dump(freeze_bn_trace(*freeze_bn_case(ref.DeepSpeech)), f)
+        f.write('\n')
+
+
 def main():
-    """``make_golden.py`` regenerates everything; ``make_golden.py ref_full_b8.npz ...`` only the named fixtures."""
+    """``make_golden.py`` regenerates everything; ``make_golden.py ref_full_b8.npz ...`` only the named fixtures
+    (``ref_configs.json`` / ``ref_freeze_bn.json`` are written together, by naming either)."""
     ref = load_reference_model_module()
     for name, kw in CASES.items():
         if sys.argv[1:] and name not in sys.argv[1:]:
             continue
         kw = dict(kw)
         run_case(ref, name, kw.pop('model_kwargs'), **kw)
+    if not sys.argv[1:] or {'ref_configs.json', 'ref_freeze_bn.json'} & set(sys.argv[1:]):
+        write_host_fixtures(ref)
 
 
 if __name__ == '__main__':

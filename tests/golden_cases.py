@@ -26,10 +26,15 @@ def case_inputs(name):
 
 
 def check_against_golden(g, logits, loss_sum, grads, buffers, probs, logit_tol, prob_tol, gnorm_rtol, gsample_rtol,
-                         buf_rtol=1e-4, buf_atol=1e-5):
-    """logits / probs: full (B,T,A) numpy arrays of the implementation under test; grads / buffers: name -> array."""
+                         buf_rtol=1e-4, buf_atol=1e-5, noise=None):
+    """logits / probs: full (B,T,A) numpy arrays of the implementation under test; grads / buffers: name -> array.
+    ``noise``: the implementation's own fp32 round-off on this machine, as ``fp32_noise`` returns it (``None``: not
+    measured); every tolerance then grows by twice it -- the fixture's fp32 numbers and the implementation's are each that
+    far from the exact ones, on different elements, and with another accumulation order (another CPU, another thread
+    count) than the fixture's."""
+    nz = (lambda key: 2.0 * noise.get(key, 0.0)) if noise else (lambda key: 0.0)
     ts = int(g['tstride']) if 'tstride' in g.files else 1
-    np.testing.assert_allclose(logits[:, ::ts], g['logits'], rtol=0, atol=logit_tol)
+    np.testing.assert_allclose(logits[:, ::ts], g['logits'], rtol=0, atol=logit_tol + nz('logits'))
     ref_loss = float(g['loss_sum'])
     assert abs(loss_sum - ref_loss) <= 1e-4 * abs(ref_loss), (loss_sum, ref_loss)
     for k, gr in grads.items():
@@ -41,17 +46,17 @@ def check_against_golden(g, logits, loss_sum, grads, buffers, probs, logit_tol, 
             scale = max(1.0, float(g['gnorm_' + k.replace('bias', 'weight')]) / 100.0)
             assert gn < 1e-2 * scale and ref_gn < 1e-2 * scale, k
             continue
-        assert abs(gn - ref_gn) <= gnorm_rtol * ref_gn + 1e-6, (k, gn, ref_gn)
+        assert abs(gn - ref_gn) <= gnorm_rtol * ref_gn + 1e-6 + nz('gnorm:' + k), (k, gn, ref_gn)
         flat = gr.reshape(-1)
         stride = max(1, flat.shape[0] // 1024)
         ref = g['gsample_' + k]
         # the reference's own fp32 gradient is ``gnoise`` away from the exact (float64) one: allow the same distance
-        noise = 2.0 * float(g['gnoise_' + k]) if 'gnoise_' + k in g.files else 0.0
+        gnoise = 2.0 * float(g['gnoise_' + k]) if 'gnoise_' + k in g.files else 0.0
         np.testing.assert_allclose(flat[::stride][:1024], ref, rtol=gsample_rtol,
-                                   atol=max(gsample_rtol * np.abs(ref).max(), noise) + 1e-7, err_msg=k)
+                                   atol=max(gsample_rtol * np.abs(ref).max(), gnoise) + 1e-7 + nz('grad:' + k), err_msg=k)
     for k, v in buffers.items():
-        np.testing.assert_allclose(v, g['buf_' + k], rtol=buf_rtol, atol=buf_atol, err_msg=k)
-    np.testing.assert_allclose(probs[:, ::ts], g['probs'], rtol=0, atol=prob_tol)
+        np.testing.assert_allclose(v, g['buf_' + k], rtol=buf_rtol, atol=buf_atol + nz('buf:' + k), err_msg=k)
+    np.testing.assert_allclose(probs[:, ::ts], g['probs'], rtol=0, atol=prob_tol + nz('probs'))
     if 'argmax' in g.files:
         am = probs.argmax(-1)
         sizes = g['out_sizes']
@@ -61,3 +66,21 @@ def check_against_golden(g, logits, loss_sum, grads, buffers, probs, logit_tol, 
         bad = valid & ~(exact | tie_ok)
         assert not bad.any(), 'argmax differs from the reference on %d confident frames' % int(bad.sum())
         assert (exact | ~valid).mean() > 0.97
+
+
+def fp32_noise(out32, out64):
+    """Per-quantity max |fp32 - fp64| of one implementation run at both precisions from the same weights and inputs
+    (``out*``: dicts with 'logits', 'probs', 'grads', 'bufs' and optionally 'inter'), in the keys ``check_against_golden``
+    reads: 'logits', 'probs', 'grad:<name>', 'gnorm:<name>', 'buf:<name>', 'inter:<name>'."""
+    def d(a, b):
+        return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
+    out = {'logits': d(out32['logits'], out64['logits']), 'probs': d(out32['probs'], out64['probs'])}
+    for k in out32['grads']:
+        out['grad:' + k] = d(out32['grads'][k], out64['grads'][k])
+        out['gnorm:' + k] = abs(float(np.sqrt((out32['grads'][k].astype(np.float64) ** 2).sum()))
+                                - float(np.sqrt((out64['grads'][k].astype(np.float64) ** 2).sum())))
+    for k in out32['bufs']:
+        out['buf:' + k] = d(out32['bufs'][k], out64['bufs'][k])
+    for k in out32.get('inter', {}):
+        out['inter:' + k] = d(out32['inter'][k], out64['inter'][k])
+    return out

@@ -87,10 +87,10 @@ def test_configs_and_model_factory():
     assert abs(sch.gamma - 0.909090909) < 1e-12
     assert expand_values({'a': ['{x}/b', {'c': '{x}'}]}, x='r') == {'a': ['r/b', {'c': 'r'}]}
 
-# Every leaf value of the eight shipped configs, as /root/reference/scripts/<same name>.json has it (a literal table: the
-# reference tree does not travel).  `training.finetune` of pt_BR-finetune-freeze is `true` there
-# (/root/reference/scripts/pt_BR-finetune-freeze.json:12): it is what makes train.py call finetune_model, the only caller of
-# _freeze_layers, and start from epoch 0 with a fresh optimizer (train.py:142-167).
+# Every leaf value of the eight shipped configs, as the reference's scripts/<same name>.json has it (a literal table; the
+# reference's own files are stored under tests/golden/ref_configs.json).  `training.finetune` of pt_BR-finetune-freeze is
+# `true` there (the reference's scripts/pt_BR-finetune-freeze.json:12): it is what makes train.py call finetune_model, the
+# only caller of _freeze_layers, and start from epoch 0 with a fresh optimizer (train.py:142-167).
 _SGD = {'optimizer.name': 'SGD', 'optimizer.params.lr': 3e-4, 'optimizer.params.momentum': 0.9,
         'optimizer.params.nesterov': True, 'scheduler.name': 'ExponentialLR'}
 _PT = dict(_SGD, **{'training.num_epochs': 100, 'training.batch_size': 32, 'training.max_norm': 400, 'training.augment': True,
@@ -134,9 +134,14 @@ def test_shipped_configs_hold_the_reference_values():
         assert got == want, (name, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)})
         for k, v in want.items():                                  # 400 vs 400.0, true vs 1 would compare equal
             assert type(got[k]) is type(v), (name, k)
-    if os.path.isdir('/root/reference/scripts'):                   # in the build container: the table against the files
-        for name, want in SHIPPED_CONFIGS.items():
-            assert _leaves(json.load(open('/root/reference/scripts/%s.json' % name))) == want, name
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_configs.json')) as f:   # the table against the reference's files
+        ref = json.load(f)
+    assert sorted(ref) == sorted(SHIPPED_CONFIGS)
+    for name, want in SHIPPED_CONFIGS.items():
+        got = _leaves(ref[name])
+        assert got == want, name
+        for k, v in want.items():
+            assert type(got[k]) is type(v), (name, k)
 
 
 def test_finetune_surgery_and_freeze():
@@ -163,33 +168,26 @@ def test_finetune_surgery_and_freeze():
 
 
 def test_reference_freeze_leaves_batchnorm_training_under_its_update_step():
-    """What ``freeze_layers`` does to BatchNorm in the reference, on stock torch modules (and, in the build container, on the
-    reference's own ``DeepSpeech``): ``_freeze_layers`` applies ``batch_norm_eval_mode`` to the layer
-    (training_utils.py:52-54,73), and ``_update`` calls ``model.train()`` before every forward pass (codes/engine.py:51) --
-    ``Module.train`` recurses, so the frozen layer's BatchNorm normalises with batch statistics and moves its running
-    estimates during training.  The product does the same (Trainer.update), see test_fused_step_with_param_groups_and_frozen_conv."""
-    nets = []
+    """What ``freeze_layers`` does to BatchNorm in the reference, on stock torch modules, checked against what the
+    reference's own ``DeepSpeech`` did (tests/golden/ref_freeze_bn.json, same seeded weights and input):
+    ``_freeze_layers`` applies ``batch_norm_eval_mode`` to the layer (training_utils.py:52-54,73), and ``_update`` calls
+    ``model.train()`` before every forward pass (codes/engine.py:51) -- ``Module.train`` recurses, so the frozen layer's
+    BatchNorm normalises with batch statistics and moves its running estimates during training.  The product does the same
+    (Trainer.update), see test_fused_step_with_param_groups_and_frozen_conv."""
     from oracle.model import OracleDeepSpeech
-    nets.append(OracleDeepSpeech(rnn_hidden_size=16, num_rnn_layers=1))
-    if os.path.isdir('/root/reference/codes'):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('ref_model_for_freeze', '/root/reference/codes/model.py')
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-        nets.append(ref.DeepSpeech(rnn_hidden_size=16, num_rnn_layers=1))
-    for net in nets:
-        def batch_norm_eval_mode(m):
-            if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
-                m.eval()
-        net.conv.apply(batch_norm_eval_mode)
-        for p in net.conv.parameters():
-            p.requires_grad = False
-        assert not net.conv[1].training
-        net.train()                                              # codes/engine.py:51
-        assert net.conv[1].training and net.conv[4].training
-        before = net.conv[1].running_mean.clone()
-        net(torch.randn(2, 60, 161))
-        assert int(net.conv[1].num_batches_tracked) == 1 and not torch.equal(net.conv[1].running_mean, before)
+    from tests.golden.make_golden import freeze_bn_case, freeze_bn_trace
+    got = freeze_bn_trace(*freeze_bn_case(OracleDeepSpeech))
+    assert got['training_after_freeze'] == [False, False]
+    assert got['training_after_train'] == [True, True]                    # codes/engine.py:51
+    assert got['num_batches_tracked'] == [1, 1] and got['running_mean'][0] != got['running_mean_before'][0]
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_freeze_bn.json')) as f:
+        ref = json.load(f)
+    assert sorted(got) == sorted(ref)
+    for k, v in ref.items():
+        if k.startswith('running_'):
+            np.testing.assert_allclose(np.array(got[k]), np.array(v), rtol=1e-5, atol=1e-6, err_msg=k)
+        else:
+            assert got[k] == v, k
 
 
 def test_checkpoint_roundtrip(tmp_path):
@@ -563,6 +561,68 @@ def test_bench_gpus_n_starts_its_own_ranks(monkeypatch, capsys):
     assert seen['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs DIR: the last step's loss and gradient norm and the same seeded sample of the parameters,
+    gradient and momentum in every run, as float32 / float64 .npy files of at most 64 MB in all (here on a small model on
+    the CPU: the helper only reads the model's flat buffers)."""
+    import types
+    from codes.model import DeepSpeech
+    bench, _ = _load_bench()
+    model = DeepSpeech(rnn_hidden_size=32, num_rnn_layers=2)
+    model._ensure_flat()
+    torch.manual_seed(3)
+    model._flat_p.data.normal_()
+    model.flat_grad().normal_()
+    trainer = types.SimpleNamespace(last_grad_norm=12.5, _buf=torch.randn_like(model._flat_p))
+    names = bench.dump_outputs(str(tmp_path / 'a'), model, trainer, 3.25)
+    bench.dump_outputs(str(tmp_path / 'b'), model, trainer, 3.25)
+    assert set(names) == {'loss', 'grad_norm', 'params_sample', 'grad_sample', 'momentum_sample', 'sample_index',
+                          'bn_running_mean', 'bn_running_var'}
+    got = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in names}
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == sorted(n + '.npy' for n in names)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for n in names:
+        assert np.array_equal(got[n], np.load(str(tmp_path / 'b' / (n + '.npy')))), n
+    assert got['loss'].tolist() == [3.25] and got['grad_norm'].tolist() == [12.5]
+    idx = got['sample_index'].astype(np.int64)
+    n = model._flat_p.numel()
+    assert len(idx) == min(n, bench.DUMP_SAMPLE) and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(got['params_sample'], model._flat_p.detach().numpy()[idx])
+    assert np.array_equal(got['grad_sample'], model.flat_grad().numpy()[idx])
+    assert np.array_equal(got['momentum_sample'], trainer._buf.numpy()[idx])
+    bns = [m for m in model.modules() if hasattr(m, 'num_batches_tracked')]
+    assert len(got['bn_running_mean']) == sum(m.running_mean.numel() for m in bns)
+
+
+def test_bench_training_state_round_trip():
+    """bench.py's dump replays a step from the run's seeded state: training_state / restore_training_state must bring back
+    the parameters, the momentum, its unset flag and the BatchNorm statistics exactly, into the same tensors."""
+    import types
+    from codes.model import DeepSpeech
+    bench, _ = _load_bench()
+    model = DeepSpeech(rnn_hidden_size=32, num_rnn_layers=2)
+    model._ensure_flat()
+    trainer = types.SimpleNamespace(_buf=torch.zeros_like(model._flat_p), _first=True)
+    bns = [m for m in model.modules() if hasattr(m, 'num_batches_tracked')]
+    flat, buf = model._flat_p, trainer._buf
+    want = (flat.clone(), [(m.running_mean.clone(), m.running_var.clone(), int(m.num_batches_tracked)) for m in bns])
+    state = bench.training_state(model, trainer)
+    with torch.no_grad():
+        flat.add_(1.0)
+        buf.fill_(2.0)
+        for m in bns:
+            m.running_mean.add_(3.0)
+            m.running_var.mul_(0.5)
+            m.num_batches_tracked += 4
+    trainer._first = False
+    bench.restore_training_state(model, trainer, state)
+    assert model._flat_p is flat and trainer._buf is buf and trainer._first is True
+    assert torch.equal(flat, want[0]) and not buf.any()
+    for m, (mean, var, n) in zip(bns, want[1]):
+        assert torch.equal(m.running_mean, mean) and torch.equal(m.running_var, var) and int(m.num_batches_tracked) == n
+
+
 def test_bench_gpus_n_end_to_end_with_a_stub_launcher(tmp_path):
     """The whole door, in a real process: `python bench.py --gpus 2` with no WORLD_SIZE must reach torch.distributed.run
     (here a stub `torch/distributed/run.py`-shaped module earlier on the path is not possible without shadowing torch, so the
@@ -652,4 +712,4 @@ def test_numa_cpu_plan_on_a_two_socket_node(tmp_path):
     # data_parallel_env on a foreign environ never touches this process's affinity
     before = os.sched_getaffinity(0)
     out = du.data_parallel_env({'LOCAL_RANK': '0'})
-    assert out == {'GPU_MAX_HW_QUEUES': '3', 'NCCL_MAX_NCHANNELS': '32'} and os.sched_getaffinity(0) == before
+    assert out == du.DEFAULTS and os.sched_getaffinity(0) == before

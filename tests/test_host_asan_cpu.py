@@ -17,6 +17,12 @@ def _gcc_file(name):
     return path if r.returncode == 0 and os.path.isabs(path) and os.path.exists(path) else None
 
 
+def _preload(asan):
+    """LD_PRELOAD for the child: the sanitizer runtime first (it must come first in the link order), followed by whatever
+    the parent's environment already preloads."""
+    return ':'.join([asan] + [p for p in os.environ.get('LD_PRELOAD', '').replace(' ', ':').split(':') if p])
+
+
 def test_host_cpp_under_asan_and_ubsan():
     asan = _gcc_file('libasan.so')
     if asan is None:
@@ -24,7 +30,7 @@ def test_host_cpp_under_asan_and_ubsan():
     sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd', 'csrc'))
     import build as csrc_build
     lib = csrc_build.build_host_sanitized()
-    env = dict(os.environ, LD_PRELOAD=asan, PYTHONPATH=ROOT,
+    env = dict(os.environ, LD_PRELOAD=_preload(asan), PYTHONPATH=ROOT,
                ASAN_OPTIONS='detect_leaks=0:abort_on_error=0:halt_on_error=1', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'asan_host_worker.py'), lib], capture_output=True,
                        text=True, env=env, timeout=600)
@@ -47,6 +53,6 @@ def test_sanitizer_build_catches_an_overflow():
             'C.malloc.argtypes=[ctypes.c_size_t]; L.ds2_edit_distance.argtypes=[ctypes.c_void_p,ctypes.c_int,'
             'ctypes.c_void_p,ctypes.c_int]; a=C.malloc(16); b=C.malloc(16); ctypes.memset(a,0,16); ctypes.memset(b,0,16); '
             'print(L.ds2_edit_distance(a,4,b,5))')                    # claims 5 elements of a 4-element array
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS='detect_leaks=0:halt_on_error=1')
+    env = dict(os.environ, LD_PRELOAD=_preload(asan), ASAN_OPTIONS='detect_leaks=0:halt_on_error=1')
     r = subprocess.run([sys.executable, '-c', code, lib], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode != 0 and 'AddressSanitizer' in r.stderr, (r.returncode, r.stderr[-2000:])

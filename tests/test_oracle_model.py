@@ -1,4 +1,5 @@
 """The oracle's model restatement against the REFERENCE's own outputs (golden fixtures)."""
+import copy
 import os
 
 import numpy as np
@@ -9,40 +10,70 @@ from oracle.model import OracleDeepSpeech, conv_out_time, gru_direction_explicit
 from tests.golden.make_golden import seeded_inputs, seeded_labels
 
 
+def _oracle_step(model, x, labels, out_sizes, label_lens, bsz, intermediates=False):
+    """One train-mode forward + CTC + backward and an eval-mode forward of ``model`` (fp32 or its float64 twin)."""
+    x = x.to(next(model.parameters()).dtype)
+    model.train()
+    if intermediates:
+        logits, inter = model(x, return_intermediates=True)
+    else:
+        logits, inter = model(x), {}
+    loss = F.ctc_loss(logits.transpose(0, 1).log_softmax(-1), labels.long(), out_sizes.long(), torch.tensor(label_lens),
+                      blank=0, reduction='sum')
+    (loss / bsz).backward()
+    out = {'logits': logits.detach().numpy(), 'loss': float(loss.item()),
+           'inter': {k: v.detach().numpy() for k, v in inter.items()},
+           'grads': {k: p.grad.numpy() for k, p in model.named_parameters()},
+           'bufs': {k: v.numpy().copy() for k, v in model.state_dict().items() if 'running' in k}}
+    model.eval()
+    with torch.no_grad():
+        out['probs'] = model(x).numpy()
+    return out
+
+
+def _oracle_and_noise(model, *args, **kwargs):
+    """The fp32 oracle's step and its own fp32 round-off (``fp32_noise``: against the same step of a float64 copy)."""
+    from tests.golden_cases import fp32_noise
+    twin = copy.deepcopy(model).double()
+    out = _oracle_step(model, *args, **kwargs)
+    return out, fp32_noise(out, _oracle_step(twin, *args, **kwargs))
+
+
 def _run(golden_dir, name, kwargs, bsz, t_in, lengths, label_lens):
+    """The oracle's fp32 step against the fixture: every tolerance is widened by twice the oracle's own fp32 round-off on
+    this machine (golden_cases.check_against_golden), since the fixture holds the reference's fp32 numbers of another
+    machine's accumulation order."""
     g = np.load(os.path.join(golden_dir, name))
     model = OracleDeepSpeech(**kwargs)
     model.load_state_dict(seeded_state_dict(model, 1234))
     x = torch.from_numpy(seeded_inputs(77, bsz, t_in, lengths=lengths))
-    model.train()
-    logits, inter = model(x, return_intermediates=True)
-    assert logits.shape[1] == conv_out_time(t_in)
-    np.testing.assert_allclose(logits.detach().numpy(), g['logits'], rtol=0, atol=2e-5)
-    labels = seeded_labels(78, label_lens, 29)
-    loss = F.ctc_loss(logits.transpose(0, 1).log_softmax(-1), torch.from_numpy(labels).long(),
-                      torch.from_numpy(g['out_sizes']).long(), torch.tensor(label_lens), blank=0, reduction='sum')
-    assert abs(loss.item() - float(g['loss_sum'])) <= 1e-4 * abs(float(g['loss_sum']))
-    (loss / bsz).backward()
-    for k, p in model.named_parameters():
-        gn = np.sqrt((p.grad.numpy().astype(np.float64) ** 2).sum())
-        assert abs(gn - float(g['gnorm_' + k])) <= 1e-4 * float(g['gnorm_' + k]) + 1e-7, k
+    labels = torch.from_numpy(seeded_labels(78, label_lens, 29))
+    out, noise = _oracle_and_noise(model, x, labels, torch.from_numpy(g['out_sizes']), label_lens, bsz, intermediates=True)
+    assert out['logits'].shape[1] == conv_out_time(t_in)
+    np.testing.assert_allclose(out['logits'], g['logits'], rtol=0, atol=2e-5 + 2 * noise['logits'])
+    assert abs(out['loss'] - float(g['loss_sum'])) <= 1e-4 * abs(float(g['loss_sum']))
+    for k, gr in out['grads'].items():
+        gn = np.sqrt((gr.astype(np.float64) ** 2).sum())
+        if k in ('conv.0.bias', 'conv.3.bias'):
+            # a bias in front of a BatchNorm has an exactly-zero gradient: both sides hold only round-off (as in
+            # golden_cases.check_against_golden)
+            scale = max(1.0, float(g['gnorm_' + k.replace('bias', 'weight')]) / 100.0)
+            assert gn < 1e-2 * scale and float(g['gnorm_' + k]) < 1e-2 * scale, k
+            continue
+        assert abs(gn - float(g['gnorm_' + k])) <= 1e-4 * float(g['gnorm_' + k]) + 1e-7 + 2 * noise['gnorm:' + k], k
         if 'grad_' + k in g:
-            np.testing.assert_allclose(p.grad.numpy(), g['grad_' + k], rtol=1e-3, atol=1e-5)
-    for k, v in model.state_dict().items():
-        if 'running' in k:
-            np.testing.assert_allclose(v.numpy(), g['buf_' + k], rtol=1e-5, atol=1e-6)
-    model.eval()
-    with torch.no_grad():
-        probs = model(x)
-    np.testing.assert_allclose(probs.numpy(), g['probs'], rtol=0, atol=1e-5)
-    return g, inter
+            np.testing.assert_allclose(gr, g['grad_' + k], rtol=1e-3, atol=1e-5 + 2 * noise['grad:' + k], err_msg=k)
+    for k, v in out['bufs'].items():
+        np.testing.assert_allclose(v, g['buf_' + k], rtol=1e-5, atol=1e-6 + 2 * noise['buf:' + k], err_msg=k)
+    np.testing.assert_allclose(out['probs'], g['probs'], rtol=0, atol=1e-5 + 2 * noise['probs'])
+    return g, out, noise
 
 
 def test_tiny_model_matches_reference(golden_dir):
-    g, inter = _run(golden_dir, 'ref_tiny.npz', dict(rnn_hidden_size=32, num_rnn_layers=2), 3, 121,
-                    [121, 97, 64], [9, 6, 4])
+    g, out, noise = _run(golden_dir, 'ref_tiny.npz', dict(rnn_hidden_size=32, num_rnn_layers=2), 3, 121,
+                         [121, 97, 64], [9, 6, 4])
     for k in ('conv1', 'conv2', 'rnn0', 'rnn1'):
-        np.testing.assert_allclose(inter[k].detach().numpy(), g['inter_' + k], rtol=0, atol=2e-5)
+        np.testing.assert_allclose(out['inter'][k], g['inter_' + k], rtol=0, atol=2e-5 + 2 * noise['inter:' + k])
 
 
 def test_full_model_matches_reference(golden_dir):
@@ -85,18 +116,10 @@ def _oracle_case(golden_dir, name):
         with torch.no_grad():
             new.weight.copy_(torch.from_numpy(swap_fc_en_to_pt_br(head[1].weight.detach().numpy(), FT43_SEED)))
         head[1] = new
-    model.train()
-    logits = model(torch.from_numpy(x))
-    loss = F.ctc_loss(logits.transpose(0, 1).log_softmax(-1), torch.from_numpy(labels).long(),
-                      torch.from_numpy(g['out_sizes']).long(), torch.tensor(kw['label_lens']), blank=0, reduction='sum')
-    (loss / kw['bsz']).backward()
-    grads = {k: p.grad.numpy() for k, p in model.named_parameters()}
-    bufs = {k: v.numpy().copy() for k, v in model.state_dict().items() if 'running' in k}
-    model.eval()
-    with torch.no_grad():
-        probs = model(torch.from_numpy(x))
-    check_against_golden(g, logits.detach().numpy(), float(loss.item()), grads, bufs, probs.numpy(), logit_tol=2e-5,
-                         prob_tol=1e-5, gnorm_rtol=1e-4, gsample_rtol=1e-3, buf_rtol=1e-5, buf_atol=1e-6)
+    out, noise = _oracle_and_noise(model, torch.from_numpy(x), torch.from_numpy(labels), torch.from_numpy(g['out_sizes']),
+                                   kw['label_lens'], kw['bsz'])
+    check_against_golden(g, out['logits'], out['loss'], out['grads'], out['bufs'], out['probs'], logit_tol=2e-5,
+                         prob_tol=1e-5, gnorm_rtol=1e-4, gsample_rtol=1e-3, buf_rtol=1e-5, buf_atol=1e-6, noise=noise)
 
 
 def test_full_model_b8_matches_reference(golden_dir):
