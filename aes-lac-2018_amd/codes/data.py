@@ -1,9 +1,16 @@
 """Minibatch assembly (reference ``codes/data.py:106-166``, ``AudioDataLoader._collate_fn``).
 
-Single-task collate only (the multi-task branch is out of scope).  The output
-layout is the hot path's input contract: ``inputs (B,T_max,161)`` float32 zero padded,
+The output layout is the hot path's input contract: ``inputs (B,T_max,161)`` float32 zero padded,
 ``targets`` flat int32, ``input_percentages (B)`` float32 = T_i / float(T_max), ``target_sizes (B)`` int32.
+Multi-task (``ConcatAudioDataset`` items carry a task index, ``collate_multitask``): the same four fields as per-task
+lists in task order, ``None`` for a task with no utterance in the batch, every task padded to the BATCH-wide T_max
+(reference ``codes/data.py:106-165``).  The per-task inputs are views of ONE (B,T_max,161) tensor in task order, so the
+model's concatenation of the present tasks costs no copy.  The raw-audio path (``collate_audio_multitask``) hands on ONE
+``RawAudioBatch`` of all clips in task order with the per-task counts (``TaskCounts``, in the input-percentage slot): the device
+frontend runs once on it, and ``split_tasks`` cuts the (B,T_max,161) result into the per-task views.
 """
+import bisect
+
 import torch
 
 
@@ -23,6 +30,79 @@ def collate(batch):
         sizes[i] = len(target)
         flat.extend(target)
     return inputs, torch.tensor(flat, dtype=torch.int), pct, sizes
+
+
+def collate_multitask(batch, num_tasks):
+    """batch: list of (spect (T_i,F), labels list[int], task) -> (inputs, targets, input_percentages, target_sizes), each a
+    list of ``num_tasks`` entries (``None`` for an absent task), utterances grouped by task in batch order."""
+    t_max, nfreq = max(batch, key=lambda s: s[0].shape[0])[0].shape
+    order = [[k for k, b in enumerate(batch) if b[2] == task] for task in range(num_tasks)]
+    inputs = torch.zeros(len(batch), t_max, nfreq)
+    out = ([None] * num_tasks, [None] * num_tasks, [None] * num_tasks, [None] * num_tasks)
+    row = 0
+    for task, idxs in enumerate(order):
+        if not idxs:
+            continue
+        n = len(idxs)
+        pct = torch.zeros(n, dtype=torch.float)
+        sizes = torch.zeros(n, dtype=torch.int)
+        flat = []
+        for j, k in enumerate(idxs):
+            spect, target = batch[k][0], batch[k][1]
+            t_i = spect.shape[0]
+            inputs[row + j, :t_i, :].copy_(spect)
+            pct[j] = t_i / float(t_max)
+            sizes[j] = len(target)
+            flat.extend(target)
+        out[0][task] = inputs[row:row + n]
+        out[1][task] = torch.tensor(flat, dtype=torch.int)
+        out[2][task] = pct
+        out[3][task] = sizes
+        row += n
+    return out
+
+
+class TaskCounts(tuple):
+    """Per-task utterance counts of a multi-task raw-audio batch, whose clips are in task order (0: the task is absent)."""
+
+
+def split_tasks(inputs, pct, counts):
+    """(B,T_max,161) frontend output + input percentages of a batch in task order -> per-task lists (``None`` if absent):
+    views of the batch-wide tensor, percentages relative to the batch-wide T_max (codes/data.py:132-152)."""
+    xs, ps, b0 = [], [], 0
+    ready, src = getattr(inputs, '_ds2_ready', None), getattr(inputs, '_ds2_src', None)
+    for n in counts:
+        if n == 0:
+            xs.append(None)
+            ps.append(None)
+            continue
+        v = inputs[b0:b0 + n]
+        if ready is not None:                        # (a prefetcher's output: every view carries its ready event)
+            v._ds2_ready, v._ds2_src = ready, src
+        xs.append(v)
+        ps.append(pct[b0:b0 + n])
+        b0 += n
+    return xs, ps
+
+
+def collate_audio_multitask(batch, num_tasks):
+    """batch: list of (wav or PCMClip, labels, task) -> (wavs in task order, per-task targets, TaskCounts, per-task
+    target sizes); ``None`` targets / sizes for an absent task."""
+    order = [[b for b in batch if b[2] == task] for task in range(num_tasks)]
+    wavs, targets, sizes = collate_audio([(b[0], b[1]) for items in order for b in items])
+    targets_l, sizes_l, off, row = [], [], 0, 0
+    for items in order:
+        if not items:
+            targets_l.append(None)
+            sizes_l.append(None)
+            continue
+        sz = sizes[row:row + len(items)]
+        n = int(sz.sum())
+        targets_l.append(targets[off:off + n])
+        sizes_l.append(sz)
+        off += n
+        row += len(items)
+    return wavs, targets_l, TaskCounts(len(items) for items in order), sizes_l
 
 
 def collate_audio(batch):
@@ -61,6 +141,23 @@ class AudioDataset(torch.utils.data.Dataset):
         return len(self.data)
 
 
+class ConcatAudioDataset(torch.utils.data.ConcatDataset):
+    """Several ``AudioDataset`` (one per task) end to end; items are ``(audio, target, task_index)`` (reference
+    ``codes/data.py:72-93``).  ``durations`` is every dataset's list in order, ``cumulative_sizes`` as ConcatDataset."""
+
+    def __init__(self, datasets):
+        super().__init__(datasets)
+        self._durations = [d for ds in self.datasets for d in ds.durations]
+
+    def __getitem__(self, idx):
+        task = bisect.bisect_right(self.cumulative_sizes, idx)
+        return tuple(super().__getitem__(idx)) + (task,)
+
+    @property
+    def durations(self):
+        return self._durations
+
+
 class AudioDataLoader(torch.utils.data.DataLoader):
     """DataLoader whose collate is the reference's (``codes/data.py:96-166``).
 
@@ -69,8 +166,13 @@ class AudioDataLoader(torch.utils.data.DataLoader):
 
     def __init__(self, *args, **kwargs):
         raw = kwargs.pop('raw_audio', False)
-        kwargs.pop('num_tasks', None)
-        kwargs['collate_fn'] = _collate_raw if raw else _collate_spect
+        num_tasks = int(kwargs.pop('num_tasks', 1) or 1)
+        if num_tasks > 1:
+            import functools
+            kwargs['collate_fn'] = functools.partial(_collate_raw_multitask if raw else _collate_spect_multitask,
+                                                     num_tasks=num_tasks)
+        else:
+            kwargs['collate_fn'] = _collate_raw if raw else _collate_spect
         super().__init__(*args, **kwargs)
 
 
@@ -81,6 +183,14 @@ def _labels_list(t):
 
 def _collate_spect(batch):
     return collate([(s, _labels_list(t)) for s, t in batch])
+
+
+def _collate_spect_multitask(batch, num_tasks):
+    return collate_multitask([(s, _labels_list(t), int(task)) for s, t, task in batch], num_tasks)
+
+
+def _collate_raw_multitask(batch, num_tasks):
+    return collate_audio_multitask([(w, _labels_list(t), int(task)) for w, t, task in batch], num_tasks)
 
 
 def _collate_raw(batch):
@@ -120,6 +230,8 @@ class DevicePrefetcher(object):
                 inputs._ds2_ready = torch.cuda.Event()
                 inputs._ds2_ready.record(self.stream)
                 inputs._ds2_src = dev
+                if isinstance(batch[2], TaskCounts):                  # multi-task: per-task views of the one batch
+                    inputs, pct = split_tasks(inputs, pct, batch[2])
                 return (inputs, batch[1], pct, batch[3])
             dev.ready = torch.cuda.Event()
             dev.ready.record(self.stream)

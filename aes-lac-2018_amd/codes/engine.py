@@ -16,6 +16,12 @@ parameter groups -- the per-layer learning rates of ``training_utils.py:133-159`
 out): learning rate, momentum and the LR scheduler keep working through ``optimizer.param_groups``; its momentum buffers are
 views of the trainer's flat momentum buffer so ``optimizer.state_dict()`` checkpoints as before.  Any
 other optimizer falls back to ``loss.backward()`` through the model's autograd node + ``optimizer.step()``.
+
+Multi-task (``task_weights`` with more than one entry, a ``MultiTaskModel``; reference ``codes/engine.py:39-78``): a batch
+carries per-task lists (``None`` for an absent task), the step loss is sum_i w_i * sum(costs_i) / B_i over the present tasks,
+task i's CTC gradient is scaled by w_i / B_i, and the infinite-loss rule applies PER TASK: an infeasible task contributes 0
+and a zero gradient, the others are unaffected (the reference sanitises each task's loss on its own, ``:68-76``).  The same
+single readback carries every task's cost sum.
 """
 import logging
 import os
@@ -27,7 +33,7 @@ import torch.distributed as dist
 from ds2hip import ops
 
 from .ctc import ctc_costs_and_grad
-from .data import wait_ready
+from .data import TaskCounts, split_tasks, wait_ready
 
 LOG = logging.getLogger('aes-lac-2018')
 
@@ -43,21 +49,26 @@ _STATS_DIRECT = os.environ.get('DS2_STATS_DIRECT', '1') != '0'
 class PendingLoss(object):
     """The host half of a training step whose device work is already enqueued (``Trainer.update(defer=True)``)."""
 
-    def __init__(self, trainer, host, done, bsz, scale):
+    def __init__(self, trainer, host, done, bsz, scale, tasks=None):
         self.trainer, self.host, self.done, self.bsz, self.scale = trainer, host, done, bsz, scale
+        self.tasks = tasks                        # multi-task: [(task, weight, B_task)] of the present tasks, one stats slot each
         self.stream = torch.cuda.current_stream() if done is None else None   # the stream the step was queued on
         self._value = None
 
     def result(self):
         if self._value is None:
             if self.done is None:                 # the kernel wrote the slot itself: poll the memory
-                loss_sum, sumsq, timed_out, n_inf = ops.wait_step_stats(self.host, stream=self.stream)
+                vals = ops.wait_step_stats(self.host, stream=self.stream)
             else:
                 ops.spin_wait(self.done)
-                loss_sum, sumsq, timed_out, n_inf = self.host.tolist()
-            if timed_out != 0:
+                vals = self.host.tolist()
+            loss_sum, sumsq, timed_out, n_inf = vals[:4]
+            if any(vals[4 * g + 2] != 0 for g in range(len(vals) // 4)):
                 ops.raise_async_error()
             self.trainer.last_grad_norm = float(sumsq) ** 0.5 * self.scale
+            if self.tasks is not None:
+                self._value = _multitask_loss(vals, self.tasks)
+                return self._value
             loss_v = float(loss_sum) / self.bsz
             if n_inf != 0 or loss_v in (float('inf'), float('-inf')):
                 # codes/engine.py:27-30: the loss becomes 0 * loss -- reported as 0, and no utterance of the batch
@@ -74,8 +85,9 @@ class PendingLoss(object):
 
 class Trainer(object):
     def __init__(self, model, optimizer, criterion=None, device='cuda', max_norm=400, skip_n=0, frontend=None,
-                 overlap_allreduce=True):
+                 overlap_allreduce=True, task_weights=None):
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
+        self.task_weights = None if task_weights is None else [float(w) for w in task_weights]
         self.device = torch.device(device)
         self.max_norm = max_norm
         self.skip_n = skip_n
@@ -196,6 +208,8 @@ class Trainer(object):
                                're-assigned parameter): create the optimizer and the Trainer after the last change to the model')
         t0 = time.time()
         inputs, targets, input_percentages, target_sizes = batch
+        if self.task_weights is not None:
+            return self._update_multitask(t0, inputs, targets, input_percentages, target_sizes, defer)
         if self.frontend is not None and not isinstance(inputs, torch.Tensor):   # list of clips or a RawAudioBatch
             inputs, input_percentages = self.frontend(inputs)          # raw clips -> device spectrograms
         inputs = wait_ready(inputs).to(self.device, non_blocking=True)
@@ -213,6 +227,42 @@ class Trainer(object):
 
         hook = self._bucket_hook() if self.overlap else None
         costs, _ = self._forward_backward(inputs, loss_fn, hook)
+        return self._finish_step([costs], bsz, None, defer)
+
+    def _update_multitask(self, t0, inputs, targets, input_percentages, target_sizes, defer):
+        """One multi-task step: the present tasks share the base's pass; each runs its own head, CTC and inf rule."""
+        if isinstance(input_percentages, TaskCounts):      # raw clips in task order: the device frontend, once
+            inputs, input_percentages = self.frontend_split(inputs, input_percentages)
+        x, present = _join_tasks(inputs)
+        x = x.to(self.device, non_blocking=True)
+        self.data_time = time.time() - t0
+        w = self.task_weights
+        if not self._fused:
+            return self._update_autograd_multitask(x, present, targets, input_percentages, target_sizes)
+
+        def loss_fn(acts):
+            costs, grads = [], []
+            for (i, n), a in zip(present, acts):
+                out_sizes = sanitize_inputs(a.shape[0], input_percentages[i])
+                c, d = ctc_costs_and_grad(a, targets[i], out_sizes, target_sizes[i], grad_scale=w[i] / n,
+                                          zero_batch_if_inf=True)        # the inf rule, per task
+                costs.append(c)
+                grads.append(d)
+            return costs, grads
+
+        hook = self._bucket_hook() if self.overlap else None
+        costs, _ = self._forward_backward(x, loss_fn, hook, present)
+        return self._finish_step(costs, x.shape[0], [(i, w[i], n) for i, n in present], defer)
+
+    def frontend_split(self, wavs, counts):
+        """A multi-task raw-audio batch -> per-task spectrogram views and input percentages (batch-wide T_max)."""
+        if self.frontend is None:
+            raise RuntimeError('a raw-audio multi-task batch needs the trainer\'s frontend (BatchSpectrogram)')
+        return split_tasks(*self.frontend(wavs), counts)
+
+    def _finish_step(self, costs, bsz, tasks, defer):
+        """All-reduce, norm, clip + Nesterov SGD, the one readback: ``costs`` = one cost vector per stats slot."""
+        model = self.model
         gflat = model.flat_grad()
         if self.distributed:
             if self.overlap:
@@ -229,22 +279,33 @@ class Trainer(object):
         model._tick('gradient norm + clip + Nesterov SGD')
         # one launch gathers what the host needs (loss sum, grad norm^2, sticky kernel-timeout flags, inf count),
         # one device->host copy brings it over
+        nslot = len(costs)                                                # (multi-task: one 4-value slot per task)
         if self._host_stats is None:
-            self._host_stats = [torch.empty(4, dtype=torch.float64).pin_memory() for _ in range(2)]
-        slot = self._host_stats[self.iteration & 1]                       # two page-locked slots: a deferred readback
+            self._host_stats = {}
+        slots = self._host_stats.get(nslot)
+        if slots is None:
+            slots = self._host_stats[nslot] = [torch.empty(4 * nslot, dtype=torch.float64).pin_memory() for _ in range(2)]
+        slot = slots[self.iteration & 1]                       # two page-locked slots: a deferred readback
         if _STATS_DIRECT:                                                 # survives the next step's
             # the kernel writes the slot in host memory itself and the host polls it: no copy, no event (DS2_STATS_DIRECT=0
             # restores them)
             ops.arm_step_stats(slot)
-            ops.step_stats(costs, self._sumsq, slot)
+            if nslot == 1:
+                ops.step_stats(costs[0], self._sumsq, slot)
+            else:
+                for g, c in enumerate(costs):
+                    ops.step_stats(c, self._sumsq, slot[4 * g:4 * g + 4])
             done = None
         else:
-            self._stats = ops.step_stats(costs, self._sumsq, self._stats)
+            if self._stats is None or self._stats.numel() != 4 * nslot:
+                self._stats = torch.empty((nslot, 4), dtype=torch.float64, device=gflat.device)
+            for g, c in enumerate(costs):
+                ops.step_stats(c, self._sumsq, self._stats[g])
             slot.copy_(self._stats.reshape(-1), non_blocking=True)
             done = torch.cuda.Event()
             done.record()
         self.iteration += 1
-        pend = PendingLoss(self, slot, done, bsz, scale)
+        pend = PendingLoss(self, slot, done, bsz, scale, tasks)
         prev, self._pending = self._pending, pend
         if prev is not None:
             prev.result()                                                 # the previous step's sync, one step late
@@ -258,7 +319,7 @@ class Trainer(object):
         prev, self._pending = self._pending, None
         return prev.result() if prev is not None else None
 
-    def _forward_backward(self, inputs, loss_fn, hook):
+    def _forward_backward(self, inputs, loss_fn, hook, present=None):
         m = self.model
         state = {}
         # ONE fill of the whole flat gradient, on the side stream beside the forward pass (the step's first side-stream work:
@@ -283,7 +344,8 @@ class Trainer(object):
                 with torch.cuda.stream(side if side is not None else main):
                     gflat.zero_()
 
-        acts, sv = m._forward_impl(inputs.contiguous().float(), training=True, need_grad=True, after_conv=fill)
+        args = (inputs.contiguous().float(),) if present is None else (inputs.contiguous().float(), present)
+        acts, sv = m._forward_impl(*args, training=True, need_grad=True, after_conv=fill)
         costs, d_acts = loss_fn(acts)
         m._backward_impl(sv, d_acts, state['gflat'], grad_ready=hook, prezeroed=prezero)
         return costs, acts
@@ -333,6 +395,37 @@ class Trainer(object):
         self.iteration += 1
         return 0.0 if is_inf else float(loss.item())
 
+    def _update_autograd_multitask(self, x, present, targets, input_percentages, target_sizes):
+        """The reference's multi-task step through autograd (codes/engine.py:62-93), the inf rule per task."""
+        out = self.model.run_concat(x, present)
+        crits = self.criterion if isinstance(self.criterion, (list, tuple)) else [self.criterion] * len(self.task_weights)
+        total, value = None, 0.0
+        for i, n in present:
+            o = out[i]
+            out_sizes = sanitize_inputs(o.shape[1], input_percentages[i])
+            loss = (crits[i](o.transpose(0, 1), targets[i], out_sizes, target_sizes[i]) / n).sum()
+            v = float(loss.item())
+            if v in (float('inf'), float('-inf')):
+                LOG.warning('WARNING: received an inf loss for task %d, setting its loss value to 0', i)
+                loss = 0 * loss
+            else:
+                value += self.task_weights[i] * v
+            loss = self.task_weights[i] * loss
+            total = loss if total is None else total + loss
+        self.optimizer.zero_grad()
+        total.backward()
+        if self.world > 1:
+            for p in self.model.parameters():
+                if p.grad is not None:
+                    dist.all_reduce(p.grad)
+                    p.grad.div_(self.world)
+        self.last_grad_norm = float(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_norm))
+        self.optimizer.step()
+        torch.cuda.synchronize()
+        ops.check_async_errors()
+        self.iteration += 1
+        return value
+
     def run(self, loader, num_epochs=1, on_iteration=None, on_epoch=None):
         """Epoch loop; the per-step readback is deferred by one step (``update(defer=True)``), so ``on_iteration`` for
         step i runs once step i + 1 has been enqueued."""
@@ -349,6 +442,29 @@ class Trainer(object):
                     on_iteration(self, epoch, prev[0], _resolved(prev[1]))
             if on_epoch is not None:
                 on_epoch(self, epoch)
+
+
+def _multitask_loss(vals, tasks):
+    """sum_i w_i * (sum of task i's costs) / B_i; an infinite task counts 0 (its gradient was zeroed on the device)."""
+    total = 0.0
+    for g, (task, w, n) in enumerate(tasks):                    # slot g = the g-th PRESENT task
+        loss_v = float(vals[4 * g]) / n
+        if vals[4 * g + 3] != 0 or loss_v in (float('inf'), float('-inf')):
+            LOG.warning('WARNING: received an inf loss for task %d, setting its loss value to 0', task)
+            continue
+        total += w * loss_v
+    return total
+
+
+def _join_tasks(inputs):
+    """The present tasks' inputs concatenated along the batch axis in task order (codes/model.py:241) and ((task, B_i), ...)."""
+    present = tuple((i, int(x.shape[0])) for i, x in enumerate(inputs) if x is not None)
+    if not present:
+        raise ValueError('a multi-task batch with every task absent')
+    parts = [wait_ready(x) for x in inputs if x is not None]
+    if len(parts) > 1 and len(set(p.device for p in parts)) > 1:
+        parts = [p.to('cpu') for p in parts]
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)), present
 
 
 def _resolved(loss):
@@ -370,10 +486,14 @@ class Evaluator(object):
             return out, targets.to('cpu'), out_sizes, target_sizes.to('cpu')
 
     def run(self, loader):
-        """Returns dict(ctcloss, wer, cer) with the training-time metric definitions:
+        """Returns dict(ctcloss, wer, cer) with the training-time metric definitions (multi-task: per-task lists, see
+        ``run_multitask``):
         ctcloss = sum of CTC costs on the eval-mode outputs (probabilities, soft-maxed again inside the loss,
         ``codes/metrics.py:49-51``) / utterances; wer / cer = mean over utterances of distance / reference
         length, x100 (``codes/metrics.py:114-132,143-162``)."""
+        from .model import MultiTaskModel
+        if isinstance(self.model, MultiTaskModel):
+            return self.run_multitask(loader)
         tot_loss, n_utt, wer_sum, cer_sum = 0.0, 0, 0.0, 0.0
         for batch in loader:
             out, targets, out_sizes, target_sizes = self.inference(batch)
@@ -397,13 +517,72 @@ class Evaluator(object):
         return {'ctcloss': tot_loss / n, 'wer': 100.0 * wer_sum / n, 'cer': 100.0 * cer_sum / n}
 
 
+    def run_multitask(self, loader):
+        """Per-task lists of ctcloss, wer and cer (the reference's ``ConcatMetrics``, codes/metrics.py:6-34): each task's
+        metrics over its own utterances, with that task's decoder (``decoder``: one per task); a task that saw no
+        utterance reports 0."""
+        ntask = self.model.num_tasks
+        decoders = self.decoder if isinstance(self.decoder, (list, tuple)) else [self.decoder] * ntask
+        tot = [[0.0, 0, 0.0, 0.0] for _ in range(ntask)]            # loss sum, utterances, wer sum, cer sum
+        self.model.eval()
+        for inputs, targets, input_percentages, target_sizes in loader:
+            x, present = _join_tasks(inputs)
+            with torch.no_grad():
+                outs = self.model.run_concat(x.to(self.device), present)
+            for i, _ in present:
+                out = outs[i]
+                out_sizes = sanitize_inputs(out.shape[1], input_percentages[i])
+                tgt, tsz = targets[i].to('cpu'), target_sizes[i].to('cpu')
+                costs, _ = ctc_costs_and_grad(out.transpose(0, 1).contiguous(), tgt, out_sizes, tsz)
+                acc = tot[i]
+                acc[0] += float(costs.sum().item())
+                acc[1] += out.shape[0]
+                dec = decoders[i]
+                if dec is not None:
+                    w, c = _wer_cer(dec, out, out_sizes, tgt, tsz)
+                    acc[2] += w
+                    acc[3] += c
+        ops.check_async_errors()
+        res = {'ctcloss': [], 'wer': [], 'cer': []}
+        for loss, n, w, c in tot:
+            res['ctcloss'].append(loss / n if n else 0)
+            res['wer'].append(100.0 * w / n if n else 0)
+            res['cer'].append(100.0 * c / n if n else 0)
+        return res
+
+
+def _wer_cer(decoder, out, out_sizes, targets, target_sizes):
+    """Sums over the batch of per-utterance WER and CER fractions (codes/metrics.py:114-132,143-162)."""
+    hyps, _ = decoder.decode(out, out_sizes)
+    off, wer_sum, cer_sum = 0, 0.0, 0.0
+    for i in range(out.shape[0]):
+        n = int(target_sizes[i])
+        ref = decoder.convert_to_strings([targets[off:off + n]])[0][0]
+        off += n
+        hyp = hyps[i][0]
+        nw, nc = len(ref.split()), len(ref)
+        w, c = decoder.wer(hyp, ref), decoder.cer(hyp, ref)
+        wer_sum += w / nw if nw else w
+        cer_sum += c / nc if nc else c
+    return wer_sum, cer_sum
+
+
 def create_trainer(model, optimizer, criterion, device, **kwargs):
-    """Same call as the reference (``train.py:199-200``): kwargs carry max_norm, skip_n, task_weights..."""
-    if len(kwargs.get('task_weights', [1])) > 1:
-        raise NotImplementedError('multi-task training is out of scope (SURVEY.md section 2)')
-    crit = criterion[0] if isinstance(criterion, (list, tuple)) else criterion
+    """Same call as the reference (``train.py:199-200``): kwargs carry max_norm, skip_n, task_weights...  More than one task
+    weight builds the multi-task trainer (the model must be a ``MultiTaskModel`` with one head per weight)."""
+    from .model import MultiTaskModel
+    weights = list(kwargs.get('task_weights', [1]) or [1])
+    multi = isinstance(model, MultiTaskModel)
+    if multi != (len(weights) > 1) or (multi and len(weights) != model.num_tasks):
+        raise ValueError('task_weights has %d entries for a model with %s: give one weight per task' %
+                         (len(weights), '%d heads' % model.num_tasks if multi else 'one classifier'))
+    if multi:
+        crit = list(criterion) if isinstance(criterion, (list, tuple)) else criterion
+    else:
+        crit = criterion[0] if isinstance(criterion, (list, tuple)) else criterion
     return Trainer(model, optimizer, crit, device, max_norm=kwargs.get('max_norm', 400),
-                   skip_n=kwargs.get('skip_n', 0), frontend=kwargs.get('frontend', None))
+                   skip_n=kwargs.get('skip_n', 0), frontend=kwargs.get('frontend', None),
+                   task_weights=weights if multi else None)
 
 
 def create_evaluator(model, metrics=None, device='cuda', decoder=None):

@@ -16,7 +16,12 @@ Parameters live in one flat fp32 buffer (views), laid out so that both direction
 of a layer are adjacent: one MFMA GEMM produces the gate pre-activations of both directions and one
 fused kernel applies clip + Nesterov SGD to everything.
 
-Out of scope: unidirectional + Lookahead, LSTM/RNN cells, multi-task heads.
+Multi-task (reference ``codes/model.py:182-253``): ``DeepSpeech(include_classifier=False)`` is the shared base -- its forward
+returns the summed directions (T,B,H) -- and ``MultiTaskModel(base, heads)`` puts one ``SequenceWiseClassifier`` per language on
+it.  The heads' parameters live in the base's flat buffers (after the base's own), their BatchNorms run as ONE segmented launch
+per stage for all tasks (``ds2_bn1d_seg_*``) and each head's FC is a plain GEMM on its task's packed rows.
+
+Out of scope: unidirectional + Lookahead, LSTM/RNN cells.
 """
 import math
 import os
@@ -112,7 +117,7 @@ class _DS2Function(torch.autograd.Function):
     def forward(ctx, model, x, *params):
         acts, saved = model._forward_impl(x, training=True, need_grad=True)
         ctx.model, ctx.saved = model, saved
-        return acts
+        return model._top(acts)
 
     @staticmethod
     def backward(ctx, d_acts):
@@ -138,8 +143,8 @@ class DeepSpeech(nn.Module):
         super().__init__()
         if isinstance(rnn_type, str):
             rnn_type = getattr(torch.nn, rnn_type.upper())
-        if rnn_type is not nn.GRU or not bidirectional or not include_classifier:
-            raise NotImplementedError('the MI355X path implements the bidirectional-GRU classifier model only '
+        if rnn_type is not nn.GRU or not bidirectional:
+            raise NotImplementedError('the MI355X path implements the bidirectional-GRU model only '
                                       '(every BASELINE config); see SURVEY.md section 2 row 1')
         if rnn_hidden_size % 8 != 0:
             raise ValueError('rnn_hidden_size must be a multiple of 8')
@@ -168,8 +173,9 @@ class DeepSpeech(nn.Module):
             rnns.append((str(i + 1), BatchRNN(rnn_hidden_size, rnn_hidden_size)))
         self.rnns = nn.Sequential(OrderedDict(rnns))
         self.lookahead = None
-        self.fc = nn.Sequential(SequenceWise(nn.Sequential(_BatchNormParams(rnn_hidden_size),
-                                                           _LinearParams(rnn_hidden_size, num_classes))))
+        if include_classifier:         # (the reference has no ``fc`` at all without a classifier: codes/model.py:176-179)
+            self.fc = nn.Sequential(SequenceWise(nn.Sequential(_BatchNormParams(rnn_hidden_size),
+                                                               _LinearParams(rnn_hidden_size, num_classes))))
         self._flat_p = None
         self._flat_g = None
         self._plist, self._offsets = [], []
@@ -186,9 +192,16 @@ class DeepSpeech(nn.Module):
                 order += [layer.batch_norm.module.weight, layer.batch_norm.module.bias]
             r = layer.rnn
             order += [r.weight_ih_l0, r.weight_ih_l0_reverse, r.weight_hh_l0, r.weight_hh_l0_reverse]
-        head = self.fc[0].module
-        order += [head[0].weight, head[0].bias, head[1].weight]
+        if self._include_classifier:
+            head = self.fc[0].module
+            order += [head[0].weight, head[0].bias, head[1].weight]
+        for cls in self.__dict__.get('_flat_heads', ()):          # a MultiTaskModel's heads: after the base, in task order
+            head = cls.fc[0].module
+            order += [head[0].weight, head[0].bias, head[1].weight]
         return order
+
+    def _flat_roots(self):
+        return [self] + list(self.__dict__.get('_flat_heads', ()))
 
     def flatten_parameters(self):
         """(Re)pack every parameter into one contiguous fp32 buffer; parameters become views of it."""
@@ -212,7 +225,7 @@ class DeepSpeech(nn.Module):
         """What the fast path of ``_ensure_flat`` checks: every (parent, child name, child) edge of the module tree and, for
         every parameter of the flat order, (owner module, name, parameter object, offset)."""
         edges, owners = [], {}
-        for parent in self.modules():
+        for parent in (m for root in self._flat_roots() for m in root.modules()):
             for nm, child in parent._modules.items():
                 edges.append((parent, nm, child))
             for nm, prm in parent._parameters.items():
@@ -293,6 +306,8 @@ class DeepSpeech(nn.Module):
             acts = _DS2Function.apply(self, x, *self._plist)
         else:
             acts, _ = self._forward_impl(x, training=self.training, need_grad=False)
+        if not self._include_classifier:
+            return acts if acts.dim() == 3 else self._top(acts)      # (T,B,H): directions summed, codes/model.py:206
         out = acts.transpose(0, 1)                                   # (B,T,A) view, as codes/model.py:201
         if not self.training:
             t, b, a = acts.shape
@@ -326,7 +341,8 @@ class DeepSpeech(nn.Module):
         if training and model_training:
             mods = self.__dict__.get('_bn_walk')
             if mods is None:                               # the module tree is static (_ensure_flat drops this on a swap)
-                mods = self.__dict__['_bn_walk'] = [m for m in list(self.rnns.modules()) + list(self.fc.modules())
+                top = list(self.fc.modules()) if self._include_classifier else []
+                mods = self.__dict__['_bn_walk'] = [m for m in list(self.rnns.modules()) + top
                                                     if isinstance(m, _BatchNormParams)]
             for mod in mods:
                 if not mod.training:
@@ -400,6 +416,9 @@ class DeepSpeech(nn.Module):
             rec.update(xin=xin, gates=gates, ghn=ghn, hout=hout, coef=coef)
             layers.append(rec)
             prev_h = hout
+        if not self._include_classifier:               # the shared base of a multi-task model: the top layer's (2,T,B,H)
+            sv['layers'] = layers
+            return prev_h, (sv if need_grad else None)
         head = self.fc[0].module
         mi = ops.bn1d_stats(prev_h[0], prev_h[1], rows, hid, head[0].running_mean, head[0].running_var, training)
         xf = ops.bn1d_apply(prev_h[0], prev_h[1], mi, head[0].weight, head[0].bias, rows, hid)
@@ -409,6 +428,13 @@ class DeepSpeech(nn.Module):
         self._tick('head: BatchNorm + FC (forward)')
         sv.update(layers=layers, mi_fc=mi, xf=xf)
         return acts, (sv if need_grad else None)
+
+    def _top(self, acts):
+        """What ``forward`` hands on: the classifier's (T,B,A), or the base's (2,T,B,H) top layer summed to (T,B,H)."""
+        if self._include_classifier:
+            return acts
+        _, t, b, h = acts.shape
+        return ops.add2(acts[0], acts[1]).view(t, b, h)
 
     def _pair(self, p_fwd, p_rev):
         """The two directions' weights are adjacent in the flat buffer: return them as one (2*rows, cols) matrix."""
@@ -443,16 +469,19 @@ class DeepSpeech(nn.Module):
         main = torch.cuda.current_stream()
         self._tick('CTC loss + gradient')
         main.wait_event(sv['w_hh_t_ready'])
-        head = self.fc[0].module
-        d2 = d_acts.reshape(rows, ncls)
-        ops.gemm(d2, sv['xf'], trans_a=True, out=gv(head[1].weight), split_k=0)               # dW_fc = d^T xf
-        dxf = ops.gemm(d2, head[1].weight, split_k=0)                                          # (rows,H)
-        last = sv['layers'][-1]['hout']
-        dy = ops.bn1d_bwd(last[0], last[1], dxf, sv['mi_fc'], head[0].weight, rows, hid, gv(head[0].weight),
-                          gv(head[0].bias))
-        if grad_ready is not None:
-            grad_ready(*self._span(head[0].weight, head[1].weight))
-        self._tick('head: FC + BatchNorm (backward)')
+        if self._include_classifier:
+            head = self.fc[0].module
+            d2 = d_acts.reshape(rows, ncls)
+            ops.gemm(d2, sv['xf'], trans_a=True, out=gv(head[1].weight), split_k=0)               # dW_fc = d^T xf
+            dxf = ops.gemm(d2, head[1].weight, split_k=0)                                          # (rows,H)
+            last = sv['layers'][-1]['hout']
+            dy = ops.bn1d_bwd(last[0], last[1], dxf, sv['mi_fc'], head[0].weight, rows, hid, gv(head[0].weight),
+                              gv(head[0].bias))
+            if grad_ready is not None:
+                grad_ready(*self._span(head[0].weight, head[1].weight))
+            self._tick('head: FC + BatchNorm (backward)')
+        else:                                          # d_acts = d(h) of the top layer's summed directions (T,B,H)
+            dy = d_acts.reshape(rows, hid)
         nl = len(sv['layers'])
         f4 = 4
         # The weight-gradient GEMMs of a layer (dW_ih, dW_hh) are not on the chain that feeds the next (lower) layer:
@@ -645,6 +674,208 @@ class DeepSpeech(nn.Module):
         self._ensure_flat()
         gflat = self.flat_grad()
         acts, sv = self._forward_impl(x.contiguous().float(), training=True, need_grad=True)
+        loss, d_acts = loss_fn(acts)
+        self._backward_impl(sv, d_acts, gflat)
+        return loss, acts
+
+
+# ------------------------------------------------------------------------------------ multi-task heads
+class SequenceWiseClassifier(nn.Module):
+    """One language's head (reference ``codes/model.py:210-225``): ``fc.0.module.{0,1}`` = BatchNorm1d + Linear(bias=False),
+    initialised in the reference's order.  A holder like the modules above: ``MultiTaskModel`` runs it."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.fc = nn.Sequential(SequenceWise(nn.Sequential(_BatchNormParams(in_features),
+                                                           _LinearParams(in_features, out_features))))
+
+
+class _MTFunction(torch.autograd.Function):
+    """The multi-task network as ONE autograd node: one output (T,B_i,A_i) per present task."""
+
+    @staticmethod
+    def forward(ctx, model, x, present, *params):
+        acts, saved = model._forward_impl(x, present, training=True, need_grad=True)
+        ctx.model, ctx.saved = model, saved
+        return tuple(acts)
+
+    @staticmethod
+    def backward(ctx, *d_acts):
+        model = ctx.model
+        gflat = torch.empty_like(model._flat_p)
+        model._backward_impl(ctx.saved, [d.contiguous() for d in d_acts], gflat)
+        ctx.saved = None
+        grads = [gflat[o:o + p.numel()].view_as(p) for p, o in zip(model._plist, model._offsets)]
+        return (None, None, None) + tuple(grads)
+
+
+class MultiTaskModel(nn.Module):
+    """Shared ``DeepSpeech(include_classifier=False)`` base + one ``SequenceWiseClassifier`` per task (reference
+    ``codes/model.py:228-253``, same ``state_dict`` keys: ``base_model.*``, ``heads.{i}.fc.0.module.{0,1}.*``).
+
+    ``forward(inputs)`` takes the reference's list with ``None`` for absent tasks; the present ones are concatenated along the
+    batch axis in task order, so task i owns a contiguous run of batch columns.  It returns a list: (B_i,T,A_i) activations in
+    training, softmax in eval, ``None`` for absent tasks.  An absent task's head is not run at all: its BatchNorm buffers and
+    ``num_batches_tracked`` stay as they are and its gradient is zero.
+
+    Parameters of base AND heads are views of the base's ONE flat buffer (heads after the base, in task order), so the fused
+    clip + Nesterov SGD runs once per step and a data-parallel trainer's first bucket is the heads."""
+
+    def __init__(self, base_model, heads):
+        super().__init__()
+        if not isinstance(base_model, DeepSpeech) or base_model._include_classifier:
+            raise ValueError('MultiTaskModel needs a DeepSpeech(include_classifier=False) base')
+        heads = list(heads)
+        if not 1 <= len(heads) <= 8:
+            raise ValueError('MultiTaskModel: 1 to 8 heads (the segmented BatchNorm kernels take up to 8 tasks)')
+        for h in heads:
+            if not isinstance(h, SequenceWiseClassifier) or h.in_features != base_model._rnn_hidden_size:
+                raise ValueError('every head must be a SequenceWiseClassifier(%d, num_classes)' % base_model._rnn_hidden_size)
+        self.base_model = base_model
+        self.heads = nn.ModuleList(heads)
+        base_model.__dict__['_flat_heads'] = self.heads          # (not a sub-module of the base: state_dict keys stay)
+        base_model._flat_p = None                                # re-pack with the heads on the next step
+        base_model.__dict__['_flat_sig'] = None
+
+    # the flat buffers are the base's
+    _flat_p = property(lambda self: self.base_model._flat_p)
+    _plist = property(lambda self: self.base_model._plist)
+    _offsets = property(lambda self: self.base_model._offsets)
+    overlap_wgrad = property(lambda self: self.base_model.overlap_wgrad)
+
+    def _ensure_flat(self):
+        self.base_model._ensure_flat()
+
+    def flatten_parameters(self):
+        self.base_model.flatten_parameters()
+        return self
+
+    def flat_grad(self):
+        return self.base_model.flat_grad()
+
+    def _tick(self, name):
+        self.base_model._tick(name)
+
+    def _side_stream(self, dev):
+        return self.base_model._side_stream(dev)
+
+    def _span(self, first, last):
+        return self.base_model._span(first, last)
+
+    @property
+    def num_tasks(self):
+        return len(self.heads)
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, inputs):
+        if not isinstance(inputs, (list, tuple)):
+            raise TypeError('MultiTaskModel.forward takes a list of per-task inputs (None for an absent task)')
+        if len(inputs) != len(self.heads):
+            raise ValueError('%d inputs for %d heads' % (len(inputs), len(self.heads)))
+        dev = self.base_model.conv[0].weight.device
+        if dev.type != 'cuda':
+            raise RuntimeError('MultiTaskModel runs on a ROCm device only (model.to("cuda")); there is no CPU path')
+        present = tuple((i, int(x.shape[0])) for i, x in enumerate(inputs) if x is not None)
+        if not present:
+            raise ValueError('every task is absent')
+        parts = [x for x in inputs if x is not None]
+        x = parts[0] if len(parts) == 1 else torch.cat([p.to(dev) for p in parts], dim=0)   # codes/model.py:241
+        return self.run_concat(x, present)
+
+    def run_concat(self, x, present):
+        """``forward`` on inputs already concatenated in task order: ``present`` = ((task, B_task), ...)."""
+        dev = self.base_model.conv[0].weight.device
+        if x.device != dev:
+            x = x.to(dev)
+        x = x.contiguous().float()
+        self._ensure_flat()
+        if self.training and torch.is_grad_enabled():
+            acts = _MTFunction.apply(self, x, tuple(present), *self._plist)
+        else:
+            acts, _ = self._forward_impl(x, present, training=self.training, need_grad=False)
+        out = [None] * len(self.heads)
+        for (i, _), a in zip(present, acts):
+            if self.training:
+                out[i] = a.transpose(0, 1)                                    # (B_i,T,A_i), codes/model.py:220
+            else:
+                t, b, n = a.shape
+                out[i] = ops.softmax_rows(a.reshape(t * b, n), t * b, n).view(t, b, n).transpose(0, 1)
+        return out
+
+    def _bounds(self, present):
+        bounds = [0]
+        for _, n in present:
+            bounds.append(bounds[-1] + n)
+        return bounds
+
+    def _forward_impl(self, x, present, training, need_grad, after_conv=None):
+        """x (B,T_in,161), B = sum of the present tasks' B_i -> [acts_i (T,B_i,A_i)] for the present tasks, and what backward
+        needs."""
+        base = self.base_model
+        if training and self.training:
+            for i, _ in present:
+                if not self.heads[i].fc[0].module[0].training:
+                    raise NotImplementedError('a head BatchNorm in inference mode inside a training step is not supported')
+        h, sv = base._forward_impl(x, training, need_grad, after_conv)        # (2,T,B,H) top layer
+        _, t, bsz, hid = h.shape
+        bounds = self._bounds(present)
+        assert bounds[-1] == bsz, 'present task sizes do not add up to the batch'
+        mods = [self.heads[i].fc[0].module for i, _ in present]
+        mi = ops.bn1d_seg_stats(h[0], h[1], t, bsz, hid, bounds, [m[0].running_mean for m in mods],
+                                [m[0].running_var for m in mods], training)
+        xf = ops.bn1d_seg_apply(h[0], h[1], mi, t, bsz, hid, bounds, [m[0].weight for m in mods],
+                                [m[0].bias for m in mods])                   # packed: task after task, (T,B_i,H) each
+        if training:
+            for m in mods:
+                m[0].num_batches_tracked += 1
+        acts = []
+        for g, m in enumerate(mods):
+            xg = xf[t * bounds[g]:t * bounds[g + 1]]
+            acts.append(ops.gemm(xg, m[1].weight, trans_b=True).view(t, bounds[g + 1] - bounds[g], m[1].out_features))
+        self._tick('heads: segmented BatchNorm + FC per task (forward)')
+        if sv is not None:
+            sv['mt'] = dict(h=h, mi=mi, xf=xf, present=tuple(present), bounds=bounds)
+        return acts, sv
+
+    # ------------------------------------------------------------------ backward
+    def _backward_impl(self, sv, d_acts, gflat, grad_ready=None, prezeroed=False):
+        """d_acts: one (T,B_i,A_i) gradient per present task -> every parameter's gradient in ``gflat``; an absent task's head
+        gets zeros.  ``grad_ready`` sees the heads' span first, then the base's slices as in ``DeepSpeech._backward_impl``."""
+        base = self.base_model
+        mt = sv.pop('mt')
+        h, mi, xf, present, bounds = mt['h'], mt['mi'], mt['xf'], mt['present'], mt['bounds']
+        _, t, bsz, hid = h.shape
+        gv = lambda p: base._gview(gflat, p)                                  # noqa: E731
+        torch.cuda.current_stream().wait_event(sv['w_hh_t_ready'])            # (behind the trainer's fill of gflat)
+        dxf = torch.empty((t * bsz, hid), dtype=torch.float32, device=h.device)
+        mods = []
+        for g, ((i, n), d) in enumerate(zip(present, d_acts)):
+            m = self.heads[i].fc[0].module
+            mods.append(m)
+            d2 = d.reshape(t * n, m[1].out_features)
+            ops.gemm(d2, xf[t * bounds[g]:t * bounds[g + 1]], trans_a=True, out=gv(m[1].weight), split_k=0)  # dW_i
+            ops.gemm(d2, m[1].weight, out=dxf[t * bounds[g]:t * bounds[g + 1]], split_k=0)                  # packed dxf
+        if not prezeroed:
+            here = {i for i, _ in present}
+            for i, cls in enumerate(self.heads):
+                if i not in here:
+                    m = cls.fc[0].module
+                    for p in (m[0].weight, m[0].bias, m[1].weight):
+                        gv(p).zero_()
+        dy = ops.bn1d_seg_bwd(h[0], h[1], dxf, mi, t, bsz, hid, bounds, [m[0].weight for m in mods],
+                              [gv(m[0].weight) for m in mods], [gv(m[0].bias) for m in mods])
+        if grad_ready is not None:
+            first, last = self.heads[0].fc[0].module, self.heads[-1].fc[0].module
+            grad_ready(*base._span(first[0].weight, last[1].weight))
+        self._tick('heads: FC per task + segmented BatchNorm (backward)')
+        base._backward_impl(sv, dy.view(t, bsz, hid), gflat, grad_ready=grad_ready, prezeroed=prezeroed)
+
+    def forward_backward(self, x, present, loss_fn):
+        """One fused pass: ``loss_fn([acts_i]) -> (loss, [d_acts_i])``, gradients into flat_grad() (as DeepSpeech's)."""
+        self._ensure_flat()
+        gflat = self.flat_grad()
+        acts, sv = self._forward_impl(x.contiguous().float(), present, training=True, need_grad=True)
         loss, d_acts = loss_fn(acts)
         self._backward_impl(sv, d_acts, gflat)
         return loss, acts

@@ -73,8 +73,20 @@ def load_legacy_model(ckpt):
     return model, front, T.ToLabel(labels)
 
 
-def load_model(model_path, num_classes=29, return_transforms=False, data_dir=None, return_ckpt=False):
-    ckpt = torch.load(model_path, map_location='cpu', weights_only=False)
+def checkpoint_langs(ckpt):
+    """The ``model.langs`` a loaded checkpoint was trained for (a legacy version-0.0.1 checkpoint: one language)."""
+    if ckpt.get('version') == '0.0.1':
+        return ['?']
+    args = AttrDict(ckpt['args'])
+    if 'network' in args.config:
+        return ['?']
+    return list(args.config.model.langs)
+
+
+def load_model(model_path, num_classes=29, return_transforms=False, data_dir=None, return_ckpt=False, ckpt=None):
+    """``ckpt``: the checkpoint dict already loaded from ``model_path`` (it is not read again)."""
+    if ckpt is None:
+        ckpt = torch.load(model_path, map_location='cpu', weights_only=False)
     if ckpt.get('version') == '0.0.1':
         return load_legacy_model(ckpt)
     args = AttrDict(ckpt['args'])

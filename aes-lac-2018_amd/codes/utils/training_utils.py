@@ -13,9 +13,9 @@ import os
 import torch
 
 from .. import transforms
-from ..data import AudioDataLoader, AudioDataset
-from ..model import DeepSpeech, _BatchNormParams, _LinearParams
-from ..sampler import BucketingSampler, DistributedBucketingSampler
+from ..data import AudioDataLoader, AudioDataset, ConcatAudioDataset
+from ..model import DeepSpeech, MultiTaskModel, SequenceWiseClassifier, _BatchNormParams, _LinearParams
+from ..sampler import BucketingSampler, DistributedBucketingSampler, WeightedBucketingRandomSampler
 
 LOG = logging.getLogger('aes-lac-2018')
 NUM_CLASSES = {'pt_BR': 43, 'en': 29}
@@ -44,9 +44,24 @@ def audio_scale(config):
     return (training or {}).get('audio_scale', None)
 
 
+def is_multitask(config):
+    langs = config.model.langs
+    return isinstance(langs, (tuple, set, list)) and len(langs) > 1
+
+
+def check_multitask_config(config):
+    """Refuse, when the config is loaded, what the reference's multi-task path cannot do either: its ``finetune_model`` reads
+    ``model.fc``, which a MultiTaskModel does not have (training_utils.py:87-122)."""
+    if not is_multitask(config):
+        return
+    for key, where in (('finetune', config.get('training', {}) or {}), ('freeze_layers', config.model),
+                       ('map_fc', config.model)):
+        if where.get(key, None):
+            raise ValueError('%s in a multi-task config (model.langs = %s): fine-tuning surgery replaces model.fc, which '
+                             'a multi-task model does not have -- the reference fails here too' % (key, list(config.model.langs)))
+
+
 def get_model(model_dict):
-    if isinstance(model_dict.langs, (tuple, set, list)) and len(model_dict.langs) > 1:
-        raise NotImplementedError('multi-task models are out of scope (SURVEY.md section 2 row 1)')
     params = dict(model_dict.get('params', {}) or {})
     # The drop-in covers ONE frontend geometry: 320-sample windows (20 ms at 16 kHz, 161 frequency bins) -- what every shipped
     # config and the reference's released checkpoints use.  The reference derives the model's input width for any window
@@ -56,6 +71,14 @@ def get_model(model_dict):
         raise ValueError('model.params.window_size = %r: this MI355X path implements window_size = 320 only (161 frequency '
                          'bins; conv / BatchNorm / STFT kernels are specialised for it) -- see README.md "What the drop-in '
                          'does not cover"' % (params['window_size'],))
+    if isinstance(model_dict.langs, (tuple, set, list)) and len(model_dict.langs) > 1:
+        # training_utils.py:37-44: a shared base without classifier, one head per language (NUM_CLASSES[lang]; a
+        # num_classes in params is ignored, as the reference's base ignores it)
+        params['include_classifier'] = False
+        model_dict['params'] = params
+        base = DeepSpeech(**params)
+        heads = [SequenceWiseClassifier(base._rnn_hidden_size, NUM_CLASSES[lang]) for lang in model_dict.langs]
+        return MultiTaskModel(base, heads)
     params.setdefault('num_classes', NUM_CLASSES[model_dict.langs[0]])
     model_dict['params'] = params
     return DeepSpeech(**params)
@@ -161,7 +184,7 @@ def get_data_loaders(train_transforms, val_transforms, target_transforms, args, 
     if not isinstance(target_transforms, (list, tuple)):
         target_transforms = [target_transforms]
     if len(target_transforms) != 1:
-        raise NotImplementedError('multi-task data loading is out of scope')
+        return _multitask_loaders(train_transforms, val_transforms, target_transforms, args, raw_audio)
     train_set = AudioDataset(args.data_dir, args.train_manifest[0], train_transforms, target_transforms[0])
     val_set = AudioDataset(args.data_dir, args.val_manifest[0], val_transforms, target_transforms[0])
     bsz = args.config.training.batch_size
@@ -183,3 +206,42 @@ def get_data_loaders(train_transforms, val_transforms, target_transforms, args, 
         from ..data import DevicePrefetcher
         train_loader, val_loader = DevicePrefetcher(train_loader), DevicePrefetcher(val_loader)
     return train_loader, val_loader
+
+
+def _multitask_loaders(train_transforms, val_transforms, target_transforms, args, raw_audio):
+    """One manifest per language (training_utils.py:160-210): ConcatAudioDataset, ``training.sampling`` (default 'equal')
+    through WeightedBucketingRandomSampler, or DistributedBucketingSampler over the concatenation with --distributed."""
+    n = len(target_transforms)
+    if len(args.train_manifest) != n or len(args.val_manifest) != n:
+        raise ValueError('a multi-task config with %d languages needs %d train and %d val manifests' % (n, n, n))
+    if not raw_audio and any(_has_waveform_stage(t) for t in (train_transforms, val_transforms)):
+        raise ValueError('raw_audio=False needs transforms that end in a spectrogram (gpu_frontend=False)')
+    train_set = ConcatAudioDataset([AudioDataset(args.data_dir, m, train_transforms, t)
+                                    for m, t in zip(args.train_manifest, target_transforms)])
+    val_set = ConcatAudioDataset([AudioDataset(args.data_dir, m, val_transforms, t)
+                                  for m, t in zip(args.val_manifest, target_transforms)])
+    training = args.config.training
+    bsz = training.batch_size
+    if args.distributed:
+        sampler = DistributedBucketingSampler(train_set, batch_size=bsz)
+    else:
+        sampler = WeightedBucketingRandomSampler(train_set, batch_size=bsz, sampling=training.get('sampling', 'equal'),
+                                                 num_epochs=training.num_epochs)
+    workers = args.num_workers
+    if workers > 0 and not all(_is_deferred(t) for t in (train_transforms, val_transforms)):
+        workers = 0                  # (a per-utterance transform that runs device kernels cannot live in a forked worker)
+    pin = bool(raw_audio) and torch.cuda.is_available()
+    train_loader = AudioDataLoader(train_set, num_workers=workers, batch_sampler=sampler, num_tasks=n, raw_audio=raw_audio,
+                                   pin_memory=pin)
+    val_loader = AudioDataLoader(val_set, batch_size=bsz, num_workers=workers, num_tasks=n, raw_audio=raw_audio,
+                                 pin_memory=pin)
+    if raw_audio and torch.cuda.is_available():         # the same staging as single-task: upload + frontend one bin ahead
+        from ..data import DevicePrefetcher
+        train_loader, val_loader = DevicePrefetcher(train_loader), DevicePrefetcher(val_loader)
+    return train_loader, val_loader
+
+
+def _has_waveform_stage(transform):
+    stages = getattr(transform, 'transforms', [transform])
+    return any(isinstance(t, transforms.ToTensor) for t in stages) and \
+        not any(isinstance(t, transforms.ToSpectrogram) for t in stages)

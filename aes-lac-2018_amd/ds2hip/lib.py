@@ -47,6 +47,9 @@ SIGNATURES = {
     'ds2_bn1d_stats': (_I, [_P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
     'ds2_bn1d_apply': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     'ds2_bn1d_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'ds2_bn1d_seg_stats': (_I, [_P, _P, _I, _I, _I, _I, _P, _F, _F, _I, _P, _P, _P, _P, _P]),
+    'ds2_bn1d_seg_apply': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'ds2_bn1d_seg_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'ds2_gru_bidir_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'ds2_gru_bidir_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'ds2_transpose2d': (_I, [_P, _I, _I, _P, _P]),
@@ -77,7 +80,7 @@ SIGNATURES = {
     'ds2_ctc_beam_search': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
 }
 
-ABI_VERSION = 402            # DS2_ABI_VERSION of include/ds2hip.h: the revision this table (and ops.py) is written against
+ABI_VERSION = 403            # DS2_ABI_VERSION of include/ds2hip.h: the revision this table (and ops.py) is written against
 
 _lib = None
 

@@ -396,6 +396,50 @@ def bn1d_bwd(xa, xb, dy, mi, gamma, rows, feat, dgamma, dbeta):
     return dx
 
 
+def _host_ints(vals):
+    import ctypes
+    return ctypes.cast((ctypes.c_int * len(vals))(*[int(v) for v in vals]), ctypes.c_void_p)
+
+
+def _host_ptrs(tensors):
+    """A host array of device pointers (``None`` entries pass NULL)."""
+    import ctypes
+    ptrs = []
+    for t in tensors:
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous()
+        ptrs.append(None if t is None else t.data_ptr())
+    return ctypes.cast((ctypes.c_void_p * len(ptrs))(*ptrs), ctypes.c_void_p)
+
+
+def bn1d_seg_stats(xa, xb, t, bsz, feat, bounds, running_means, running_vars, training):
+    """Per-task BatchNorm statistics over the strided rows of (T,B,F) x = xa + xb: task g owns the batch columns
+    [bounds[g], bounds[g+1]).  Returns mean_invstd (G, 2F) (ds2_bn1d_seg_stats)."""
+    g = len(bounds) - 1
+    mi = _empty((g, 2 * feat), xa)
+    lib.call('ds2_bn1d_seg_stats', xa, xb, t, bsz, feat, g, _host_ints(bounds), BN_EPS, BN_MOMENTUM, int(not training),
+             _host_ptrs(running_means), _host_ptrs(running_vars), mi, _bytes_ws(g * lib.query('ds2_bn_ws_bytes', feat), xa))
+    return mi
+
+
+def bn1d_seg_apply(xa, xb, mi, t, bsz, feat, bounds, gammas, betas):
+    """Normalised rows PACKED task after task: rows [t*bounds[g], t*bounds[g+1]) of the (T*B, F) result are task g's
+    contiguous (T, B_g, F) block (ds2_bn1d_seg_apply)."""
+    y = _empty((t * bsz, feat), xa)
+    lib.call('ds2_bn1d_seg_apply', xa, xb, mi, t, bsz, feat, len(bounds) - 1, _host_ints(bounds), _host_ptrs(gammas),
+             _host_ptrs(betas), y)
+    return y
+
+
+def bn1d_seg_bwd(xa, xb, dxf, mi, t, bsz, feat, bounds, gammas, dgammas, dbetas):
+    """Packed per-task d(xf) -> interleaved (T*B, F) d(x); each task's dgamma / dbeta overwritten (ds2_bn1d_seg_bwd)."""
+    g = len(bounds) - 1
+    dy = _empty((t * bsz, feat), xa)
+    lib.call('ds2_bn1d_seg_bwd', xa, xb, dxf, mi, t, bsz, feat, g, _host_ints(bounds), _host_ptrs(gammas), dy,
+             _host_ptrs(dgammas), _host_ptrs(dbetas), _bytes_ws(g * lib.query('ds2_bn_ws_bytes', feat), xa))
+    return dy
+
+
 # ----------------------------------------------------------------------------- GRU recurrence
 GRU_MODE = os.environ.get('DS2_GRU_MODE', 'auto')     # 'auto' | 'persistent' | 'step'
 _sync_ws = {}

@@ -39,7 +39,7 @@ const char* ds2_last_error(void);
  * have changed between revisions without a change of symbol name (round 3: an amplitude-scale argument in
  * ds2_pcm16_to_float / ds2_gain_requantize; round 4: ds2_conv2_dgrad takes the size of its workspace), so a binding built
  * against another revision mis-passes arguments.  ds2hip/lib.py refuses to load a library whose number differs. */
-#define DS2_ABI_VERSION 402
+#define DS2_ABI_VERSION 403
 int ds2_version(void);
 /* A digest of the sources the loaded binary was built from (csrc/build.py: source_id(); "unstamped" for a build made without
  * build.py).  The Python binding recomputes it from the tree beside it and refuses a binary built from other sources, so a
@@ -184,6 +184,26 @@ int ds2_bn1d_apply(const float* xa, const float* xb, const float* mean_invstd, c
 int ds2_bn1d_bwd(const float* xa, const float* xb, const float* dy, const float* mean_invstd,
                  const float* gamma, int rows, int F, float* dx, float* dgamma, float* dbeta, void* ws,
                  void* stream);
+/* Segmented sequence flavour (ABI revision 403): the G <= 8 per-task heads of the multi-task model
+ * (codes/model.py:210-253), one launch per stage for all G tasks.  x = xa (+ xb) is (T,B,F); task g owns the
+ * batch columns [bounds[g], bounds[g+1]) (bounds_host: G + 1 host ints, 0 = bounds[0] < ... < bounds[G] = B), so
+ * its rows t*B + b are strided.  Each task is normalised over its own T*B_g rows (padded frames included), as the
+ * reference's per-head BatchNorm1d on x[:, b0:b1].  The *_host arguments are host arrays of G device pointers.
+ * mean_invstd: (G, 2F), task g's mean then invstd.  ws: >= G * ds2_bn_ws_bytes(F) bytes.
+ * stats: training (use_running=0) updates each task's running_mean / running_var (both arrays may be NULL: no update);
+ * use_running=1 reads them instead. */
+int ds2_bn1d_seg_stats(const float* xa, const float* xb, int T, int B, int F, int G, const int* bounds_host,
+                       float eps, float momentum, int use_running, float* const* running_mean_host,
+                       float* const* running_var_host, float* mean_invstd, void* ws, void* stream);
+/* y PACKED (T*B, F): task g's rows form the contiguous (T, B_g, F) block at row T*bounds[g]. */
+int ds2_bn1d_seg_apply(const float* xa, const float* xb, const float* mean_invstd, int T, int B, int F, int G,
+                       const int* bounds_host, const float* const* gamma_host, const float* const* beta_host,
+                       float* y, void* stream);
+/* dxf PACKED as ds2_bn1d_seg_apply's y -> dy interleaved (T,B,F), every element written (the segments cover B);
+ * each task's dgamma, dbeta (F) overwritten. */
+int ds2_bn1d_seg_bwd(const float* xa, const float* xb, const float* dxf, const float* mean_invstd, int T, int B,
+                     int F, int G, const int* bounds_host, const float* const* gamma_host, float* dy,
+                     float* const* dgamma_host, float* const* dbeta_host, void* ws, void* stream);
 
 /* ------------------------------------------------------------------ bidirectional GRU recurrence
  * Replaces nn.GRU(bias=False, bidirectional=True) (codes/model.py:51-52,62) -- the cuDNN RNN.

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 from codes.data import AudioDataLoader, AudioDataset  # noqa: E402
 from codes.decoder import BeamCTCDecoder, GreedyDecoder  # noqa: E402
 from codes.transforms import BatchSpectrogram, waveform_scale  # noqa: E402
-from codes.utils.model_utils import load_model  # noqa: E402
+from codes.utils.model_utils import checkpoint_langs, load_model  # noqa: E402
 
 
 def main(argv=None):
@@ -32,8 +32,13 @@ def main(argv=None):
     p.add_argument('--output-path', default=None, type=str)
     args = p.parse_args(argv)
 
+    ckpt = torch.load(args.model_path, map_location='cpu', weights_only=False)      # read once, for the check and the model
+    ckpt_langs = checkpoint_langs(ckpt)
+    if len(ckpt_langs) > 1:
+        raise SystemExit('test.py: %s is a multi-task checkpoint (languages %s); test.py evaluates single-task models '
+                         'only, as the reference\'s does' % (args.model_path, ckpt_langs))
     torch.set_grad_enabled(False)
-    model, _, val_t, target_t = load_model(args.model_path, return_transforms=True, data_dir=args.data_dir)
+    model, _, val_t, target_t = load_model(args.model_path, return_transforms=True, data_dir=args.data_dir, ckpt=ckpt)
     model.eval().to('cuda')
     target_t = target_t[0]
     decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder),

@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
 from codes.ctc import CTCLoss as warp_CTCLoss  # noqa: E402
+from codes.data import TaskCounts, split_tasks  # noqa: E402
 from codes.decoder import GreedyDecoder  # noqa: E402
 from codes.engine import create_evaluator, create_trainer  # noqa: E402
 from codes.transforms import BatchSpectrogram, waveform_scale  # noqa: E402
@@ -81,7 +82,8 @@ class BestCheckpoints(object):
     """The reference's ``best_ckpt_handler`` (train.py:223-229): keep the ``n_saved`` best ``model_best-ckpt_<N>.pth`` files
     by validation CER.  ignite keeps the HIGHEST scores and the reference passes the raw CER as the score; the evident
     intent -- keep the lowest CER -- is what this does.  N counts the handler's calls (= epochs run by this process),
-    as ignite's file counter does."""
+    as ignite's file counter does.  A multi-task run's score is the per-task CER list (what the reference's
+    ``score_function`` returns for it), compared in Python list order: the first task's CER decides, ties go to the next."""
 
     def __init__(self, folder, n_saved=5):
         self.folder, self.n_saved, self.calls, self.saved = folder, n_saved, 0, []
@@ -99,6 +101,13 @@ class BestCheckpoints(object):
             if os.path.exists(worst):
                 os.remove(worst)
         return path
+
+
+def _fmt(v):
+    """A metric for the log: one value, or a multi-task run's per-task list as v0/v1/..."""
+    if isinstance(v, (list, tuple)):
+        return '/'.join('{:.3f}'.format(x) for x in v)
+    return '{:.3f}'.format(v)
 
 
 def main(argv=None):
@@ -120,6 +129,8 @@ def main(argv=None):
     with open(args.config_file, 'r', encoding='utf8') as f:
         args.config = AttrDict(json.load(f))
         args.config = expand_values(args.config, **args)
+    tu.check_multitask_config(args.config)
+    multi = tu.is_multitask(args.config)
     out_dir = os.path.join(args.save_folder, args.config.model.name)
     os.makedirs(out_dir, exist_ok=True)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s',
@@ -160,8 +171,8 @@ def main(argv=None):
 
     train_t, val_t, target_t = tu.get_default_transforms(args.data_dir, args.config)
     train_loader, val_loader = tu.get_data_loaders(train_t, val_t, target_t, args)
-    criterion = [warp_CTCLoss()]
-    decoder = GreedyDecoder(target_t[0].label_encoder)
+    criterion = [warp_CTCLoss() for _ in target_t]
+    decoder = [GreedyDecoder(t.label_encoder) for t in target_t] if multi else GreedyDecoder(target_t[0].label_encoder)
     frontend = BatchSpectrogram(device=device, scale=waveform_scale(train_t))
     for ld in (train_loader, val_loader):            # decode + augmentation + STFT of the NEXT bin run on the prefetch stream
         if hasattr(ld, 'frontend'):
@@ -176,7 +187,10 @@ def main(argv=None):
     def eval_loader(loader):
         def gen():
             for wavs, targets, pct, sizes in loader:
-                if not isinstance(wavs, torch.Tensor):               # (a prefetcher with the frontend attached yields tensors)
+                if multi:
+                    if isinstance(pct, TaskCounts):                  # (a prefetcher with the frontend attached splits them)
+                        wavs, pct = split_tasks(*frontend(wavs), pct)
+                elif not isinstance(wavs, torch.Tensor):            # (a prefetcher with the frontend attached yields tensors)
                     wavs, pct = frontend(wavs)
                 yield wavs, targets, pct, sizes
         return evaluator.run(gen())
@@ -229,10 +243,10 @@ def main(argv=None):
             for k, v in m.items():
                 hist.setdefault(k, []).append(v)
         if main_proc:
-            fmt = '\t'.join('Average {} {:.3f}'.format(k, v) for k, v in train_m.items())
+            fmt = '\t'.join('Average {} {}'.format(k, _fmt(v)) for k, v in train_m.items())
             LOG.info('Training Summary Epoch: [{}]\t{}'.format(epoch + 1, fmt))
-            LOG.info('Validation Summary Epoch: [{}]\tAverage ctcloss {:.3f}\tAverage wer {:.3f}\tAverage cer {:.3f}'
-                     .format(epoch + 1, val_m['ctcloss'], val_m['wer'], val_m['cer']))
+            LOG.info('Validation Summary Epoch: [{}]\tAverage ctcloss {}\tAverage wer {}\tAverage cer {}'
+                     .format(epoch + 1, _fmt(val_m['ctcloss']), _fmt(val_m['wer']), _fmt(val_m['cer'])))
         old_lr = optimizer.param_groups[0]['lr']
         scheduler.step()
         LOG.info('Annealing learning rate from {:.5g} to {:5g}.'.format(old_lr, optimizer.param_groups[0]['lr']))
