@@ -6,7 +6,8 @@ collapse (drop blank; drop a symbol equal to the previous FRAME's symbol) run on
 (``ds2_argmax_rows`` + ``ds2_greedy_collapse``); only the compacted ids cross to the host to become strings.
 Edit distance replaces python-Levenshtein (absent here) with ``ds2_edit_distance`` (host C++ in libds2hip.so).
 ``BeamCTCDecoder`` (CTC prefix beam search, ``ds2_ctc_beam_search``) is an addition: the reference's ``test.py:21``
-offers greedy / none only.
+offers greedy / none only.  ``DeviceBeamCTCDecoder`` runs the same search for a whole batch in one
+launch on the device (``ds2_ctc_beam_search_batch``), optionally fused with an n-gram LM (``codes.lm.NGramLM``).
 """
 import numpy as np
 import torch
@@ -117,4 +118,45 @@ class BeamCTCDecoder(GreedyDecoder):
             offsets.append([torch.IntTensor(offs[:length.value].copy())])
             scores.append(logp.value)
         self.last_log_probs = scores
+        return strings, offsets
+
+
+class DeviceBeamCTCDecoder(GreedyDecoder):
+    """CTC prefix beam search of a whole batch in one device launch, with optional n-gram LM shallow fusion (not in the
+    reference).  Ranks prefixes by ``log(p_b + p_nb) + alpha * LM + beta * N`` (``csrc/ctc_beam.hip``); ``lm=None``
+    ignores alpha and beta and gives the labels of ``BeamCTCDecoder``.  The offsets are the frames at which the labels
+    were appended on the best hypothesis's surviving lineage (``BeamCTCDecoder`` reports the frame a prefix was first
+    proposed, even by a proposal that was later pruned; the two agree unless a prefix of the best path left the beam and
+    came back).  ``decode(probs, sizes)`` takes device tensors; ``last_scores`` / ``last_ctc_log_probs`` hold the fused
+    score (with the end-of-utterance LM terms) and the CTC log-probability of each best labelling."""
+
+    def __init__(self, label_encoder, blank_index=0, beam_width=16, lm=None, alpha=0.0, beta=0.0, log_input=False):
+        super().__init__(label_encoder, blank_index)
+        if not 1 <= beam_width <= 128:
+            raise ValueError('beam_width must be in 1..128 for the device search, got %d' % beam_width)
+        self.beam_width, self.log_input = int(beam_width), bool(log_input)
+        self.lm, self.alpha, self.beta = lm, float(alpha), float(beta)
+        classes = [str(c) for c in self.label_encoder.classes_.tolist()]
+        if lm is not None and classes != lm.labels:
+            raise ValueError('the LM was built for the alphabet %r, the decoder has %r' % (lm.labels, classes))
+        self.space_id = classes.index(' ') if ' ' in classes else -1
+        self.last_scores = None
+        self.last_ctc_log_probs = None
+
+    def decode(self, probs, sizes=None):
+        if not probs.is_cuda:
+            raise RuntimeError('DeviceBeamCTCDecoder.decode runs on device tensors only')
+        bsz, t, _ = probs.shape
+        if sizes is None:
+            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
+        else:
+            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+        labels, offs, lens, score, ctc = ops.ctc_beam_search(
+            probs.detach().contiguous().float(), sizes_d, self.beam_width, self.blank_index, self.log_input, self.lm,
+            self.alpha, self.beta, self.space_id)
+        labels, offs, lens = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
+        self.last_scores = score.cpu().tolist()
+        self.last_ctc_log_probs = ctc.cpu().tolist()
+        strings = [[self._to_string(labels[b, :lens[b]])] for b in range(bsz)]
+        offsets = [[torch.IntTensor(offs[b, :lens[b]].copy())] for b in range(bsz)]
         return strings, offsets

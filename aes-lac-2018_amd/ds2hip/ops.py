@@ -614,6 +614,31 @@ def greedy_collapse(best, sizes, blank=0):
     return ids, offs, lens
 
 
+def ctc_beam_search(probs, sizes, beam_width, blank=0, log_input=False, lm=None, alpha=0.0, beta=0.0, space_id=-1):
+    """Batched CTC prefix beam search on the current stream (``ds2_ctc_beam_search_batch``).  probs (B,T,A) fp32 on the
+    device, sizes (B,) int32 on the device; ``lm`` an ``codes.lm.NGramLM`` or None.  Returns the device tensors
+    labels (B,T), offsets (B,T), lens (B,) int32 and score, ctc_logp (B,) fp32."""
+    bsz, t, a = probs.shape
+    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
+    ws = _bytes_ws(ws_bytes, probs)
+    labels = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    offsets = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    lens = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
+    score = _empty((bsz,), probs)
+    ctc = _empty((bsz,), probs)
+    if lm is None:
+        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
+    else:
+        tabs = lm.to(probs.device)
+        word = tabs.get('word')
+        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
+                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
+                   float(beta), float(lm.oov_logp))
+    lib.call('ds2_ctc_beam_search_batch', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
+             *lm_args, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc)
+    return labels, offsets, lens, score, ctc
+
+
 # ----------------------------------------------------------------------------- CTC
 def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_len, grad_scale=1.0,
                   zero_batch_if_inf=False):

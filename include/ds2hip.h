@@ -39,7 +39,7 @@ const char* ds2_last_error(void);
  * have changed between revisions without a change of symbol name (round 3: an amplitude-scale argument in
  * ds2_pcm16_to_float / ds2_gain_requantize; round 4: ds2_conv2_dgrad takes the size of its workspace), so a binding built
  * against another revision mis-passes arguments.  ds2hip/lib.py refuses to load a library whose number differs. */
-#define DS2_ABI_VERSION 403
+#define DS2_ABI_VERSION 404
 int ds2_version(void);
 /* A digest of the sources the loaded binary was built from (csrc/build.py: source_id(); "unstamped" for a build made without
  * build.py).  The Python binding recomputes it from the tree beside it and refuses a binary built from other sources, so a
@@ -308,6 +308,27 @@ int ds2_greedy_collapse(const int32_t* best, const int32_t* sizes, int B, int T,
 int ds2_edit_distance(const int32_t* a, int na, const int32_t* b, int nb);
 int ds2_ctc_beam_search(const float* probs, int T, int A, int blank, int beam_width, int log_input,
                         int32_t* out_labels, int32_t* out_offsets, int out_cap, int* out_len, float* out_logp);
+
+/* ------------------------------------------------------------------ device CTC beam search (csrc/ctc_beam.hip)
+ * Not in the reference.  One launch decodes a batch: probs (B,T,A) on the device, probabilities (log_input = 0) or
+ * log-probabilities (log_input = 1), sizes (B) int32 frames per utterance (clamped to 0..T).  Same prefix rules as
+ * ds2_ctc_beam_search, fp64 accumulation, ranked by log(p_b + p_nb) + alpha * LM + beta * N; ties -> lower candidate
+ * index (slot * A + symbol), so a run is bit-reproducible.  1 <= beam_width <= 128, A <= 128.
+ * LM (unit 0 = none: the LM arguments are ignored; 1 = char; 2 = word): ngram_table = (ngram_cap, 2) uint64 entries of
+ * codes/lm.py (key = ds2_hash of the token ids, payload = float ln p | float ln backoff << 32), order 1..8; word mode
+ * adds word_table (word_cap, 2) = hash of a word's alphabet indices -> word id, and space_id = the space label.
+ * bos_id / eos_id = the ids of <s> / </s>, unk_id = the id an out-of-vocabulary token enters the history as; it scores
+ * oov_logp (natural log).  ws >= ds2_ctc_beam_ws_bytes(B, T, beam_width) bytes (the per-utterance node arrays).
+ * Outputs: out_labels / out_offsets (B,T) int32 (the best labelling and the frame each label was appended at on its
+ * surviving lineage; zero past out_len), out_len (B), out_score (B) the fused score with the end-of-utterance terms,
+ * out_ctc_logp (B) log(p_b + p_nb) of the best labelling. */
+size_t ds2_ctc_beam_ws_bytes(int B, int T, int W);
+int ds2_ctc_beam_search_batch(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                              int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                              const void* word_table, int word_cap, int order, int unit, int bos_id, int eos_id,
+                              int unk_id, int space_id, float alpha, float beta, float oov_logp, void* ws,
+                              size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
+                              float* out_score, float* out_ctc_logp, void* stream);
 
 /* ------------------------------------------------------------------ CTC
  * Replaces warpctc_pytorch.CTCLoss (train.py:179, codes/engine.py:22, codes/metrics.py:51):

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
 from codes.data import AudioDataLoader, AudioDataset  # noqa: E402
-from codes.decoder import BeamCTCDecoder, GreedyDecoder  # noqa: E402
+from codes.decoder import BeamCTCDecoder, DeviceBeamCTCDecoder, GreedyDecoder  # noqa: E402
 from codes.transforms import BatchSpectrogram, waveform_scale  # noqa: E402
 from codes.utils.model_utils import checkpoint_langs, load_model  # noqa: E402
 
@@ -28,9 +28,22 @@ def main(argv=None):
     p.add_argument('--decoder', default='greedy', choices=['greedy', 'beam', 'none'], type=str,
                    help="'beam' (CTC prefix beam search, no LM) is an addition to the reference's greedy / none")
     p.add_argument('--beam-width', default=16, type=int)
+    p.add_argument('--lm-path', default=None, type=str,
+                   help='ARPA n-gram LM fused into --decoder beam (runs the device search; build one with '
+                        'tools/make_lm.py); default: none')
+    p.add_argument('--lm-unit', default='word', choices=['word', 'char'],
+                   help='the tokens of the --lm-path LM: words or characters (default: word)')
+    p.add_argument('--alpha', default=0.8, type=float, help='LM weight (default: 0.8; ignored without --lm-path)')
+    p.add_argument('--beta', default=1.0, type=float,
+                   help='bonus per LM token, a word or a character (default: 1.0; ignored without --lm-path)')
+    p.add_argument('--beam-device', action='store_true',
+                   help='run --decoder beam as one batched device launch (implied by --lm-path); default: the host '
+                        'search, one utterance at a time')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--output-path', default=None, type=str)
     args = p.parse_args(argv)
+    if args.lm_path and args.decoder != 'beam':
+        p.error('--lm-path needs --decoder beam: only the beam search can fuse a language model')
 
     ckpt = torch.load(args.model_path, map_location='cpu', weights_only=False)      # read once, for the check and the model
     ckpt_langs = checkpoint_langs(ckpt)
@@ -43,7 +56,16 @@ def main(argv=None):
     target_t = target_t[0]
     decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder),
                'beam': lambda: BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width),
-               'none': lambda: None}[args.decoder]()
+               'none': lambda: None}[args.decoder]
+    if args.decoder == 'beam' and (args.lm_path or args.beam_device):
+        def decoder():
+            lm = None
+            if args.lm_path:
+                from codes.lm import NGramLM
+                lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
+            return DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
+                                        beta=args.beta)
+    decoder = decoder()
     target_decoder = GreedyDecoder(target_t.label_encoder)
     dataset = AudioDataset(args.data_dir, args.manifest, transforms=val_t, target_transforms=target_t)
     loader = AudioDataLoader(dataset, batch_size=args.batch_size, num_workers=args.num_workers, raw_audio=True)
