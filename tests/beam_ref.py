@@ -77,29 +77,51 @@ class _Lm(object):
         return e + self.alpha * lp
 
 
-def beam_search(lp, blank, beam_width, lm=None, alpha=0.0, beta=0.0, space_id=-1):
-    """lp: (T, A) list of double log-probs (frame_log_probs).  Returns (labels, offsets, fused score, ctc log p)."""
+def _cut_stats(scores, k):
+    """(exact tie at the cut, smallest relative gap) for keeping the k best of ``scores`` (sorted best first): the tie is
+    ``scores[k-1] == scores[k]``; the gap is min |s - tau| / max(1, |tau|) over the scores s != tau (inf if none)."""
+    tau = scores[k - 1]
+    tie = len(scores) > k and scores[k] == tau
+    gap = math.inf
+    if math.isfinite(tau):
+        for s in scores:
+            if s != tau:
+                gap = min(gap, abs(s - tau) / max(1.0, abs(tau)))
+    return tie, gap
+
+
+def beam_search(lp, blank, beam_width, lm=None, alpha=0.0, beta=0.0, space_id=-1, stats=None):
+    """lp: (T, A) list of double log-probs (frame_log_probs).  Returns (labels, offsets, fused score, ctc log p).
+
+    ``stats``: a dict to fill with what the tie tests need.  ``stats['cut']`` gets one ``(tie, gap)`` per frame at which
+    more than ``beam_width`` candidates compete (_cut_stats of the ranked scores at the W-th); ``stats['pick']`` the same
+    for the final pick of the best entry (k = 1).  A ``gap`` far above the rounding differences of two libms means that
+    the selection does not depend on them."""
     A = len(lp[0]) if lp else 0
     L = _Lm(lm, alpha, beta, space_id) if lm is not None else None
-    # beam entries: [prefix tuple, pb, pnb, lmacc, lm state, born tuple]
-    beam = [[(), 0.0, NEG_INF, 0.0, L.start() if L else None, ()]]
+    # prefixes are interned: id 0 = the empty prefix, parent[id] and last[id] describe the others
+    parent, last_of, child = [-1], [-1], {}
+    # beam entries: (prefix id, pb, pnb, lmacc, lm state, born) with born = (frame, born of the parent) or None
+    beam = [(0, 0.0, NEG_INF, 0.0, L.start() if L else None, None)]
+    if stats is not None:
+        stats['cut'] = []
     for t, row in enumerate(lp):
-        slot = {b[0]: i for i, b in enumerate(beam)}
-        cands = []                                            # (score, index, entry)
-        for i, (pre, pb, pnb, acc, st, born) in enumerate(beam):
+        slot = {e[0]: i for i, e in enumerate(beam)}
+        cands = []                                            # (score, index, entry or (slot, symbol, pnb, lmacc, state))
+        for i, (pid, pb, pnb, acc, st, born) in enumerate(beam):
             tot = log_add(pb, pnb)
-            last = pre[-1] if pre else -1
+            last = last_of[pid]
             npb = log_add(NEG_INF, tot + row[blank])
             npnb = log_add(NEG_INF, pnb + row[last]) if last >= 0 else NEG_INF
-            p = slot.get(pre[:-1]) if pre else None
+            p = slot.get(parent[pid]) if pid else None
             if p is not None and row[last] > NEG_INF:
-                ppre, ppb, ppnb = beam[p][0], beam[p][1], beam[p][2]
-                frm = ppb if (ppre and ppre[-1] == last) else log_add(ppb, ppnb)
+                ppid, ppb, ppnb = beam[p][0], beam[p][1], beam[p][2]
+                frm = ppb if (ppid and last_of[ppid] == last) else log_add(ppb, ppnb)
                 if frm > NEG_INF:
                     npnb = log_add(npnb, frm + row[last])
-            cands.append((log_add(npb, npnb) + acc, i * A + blank, [pre, npb, npnb, acc, st, born]))
+            cands.append((log_add(npb, npnb) + acc, i * A + blank, (pid, npb, npnb, acc, st, born)))
             for c in range(A):
-                if c == blank or row[c] <= NEG_INF or (pre + (c,)) in slot:
+                if c == blank or row[c] <= NEG_INF or child.get((pid, c)) in slot:
                     continue
                 frm = pb if c == last else tot
                 if frm <= NEG_INF:
@@ -109,19 +131,42 @@ def beam_search(lp, blank, beam_width, lm=None, alpha=0.0, beta=0.0, space_id=-1
                 if L is not None:
                     d, nst = L.append(st, c)
                     nacc = acc + d
-                cands.append((log_add(NEG_INF, v) + nacc, i * A + c, [pre + (c,), NEG_INF, v, nacc, nst, born + (t,)]))
+                cands.append((log_add(NEG_INF, v) + nacc, i * A + c, (i, c, v, nacc, nst)))
         cands.sort(key=lambda x: (-x[0], x[1]))
+        if stats is not None and len(cands) > beam_width:
+            stats['cut'].append(_cut_stats([x[0] for x in cands], beam_width))
         keep = sorted(cands[:beam_width], key=lambda x: x[1])
-        beam = [e for _, _, e in keep]
-    best, best_v, best_tot = None, NEG_INF, NEG_INF
-    for pre, pb, pnb, acc, st, born in beam:
+        nbeam = []
+        for _, _, e in keep:
+            if len(e) == 5:                                   # an extension: intern its prefix
+                i, c, v, nacc, nst = e
+                ppid = beam[i][0]
+                pid = child.get((ppid, c))
+                if pid is None:
+                    pid = child[(ppid, c)] = len(parent)
+                    parent.append(ppid)
+                    last_of.append(c)
+                e = (pid, NEG_INF, v, nacc, nst, (t, beam[i][5]))
+            nbeam.append(e)
+        beam = nbeam
+    best, best_v, best_tot, ends = None, NEG_INF, NEG_INF, []
+    for pid, pb, pnb, acc, st, born in beam:
         tot = log_add(pb, pnb)
         v = tot + (L.end(acc, st) if L else 0.0)
+        ends.append(v)
         if v > best_v:
-            best, best_v, best_tot = (pre, born), v, tot
+            best, best_v, best_tot = (pid, born), v, tot
+    if stats is not None:
+        stats['pick'] = _cut_stats(sorted(ends, reverse=True), 1)
     if best is None:
-        return [], [], float(np.float32(NEG_INF)), float(np.float32(NEG_INF))
-    return list(best[0]), list(best[1]), best_v, best_tot
+        return [], [], -math.inf, -math.inf                  # NEG_INF as the device's float32 outputs
+    labels, offsets = [], []
+    pid, born = best
+    while pid:
+        labels.append(last_of[pid])
+        offsets.append(born[0])
+        pid, born = parent[pid], born[1]
+    return labels[::-1], offsets[::-1], best_v, best_tot
 
 
 def lm_score(lm, labels, alpha, beta, space_id):
