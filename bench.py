@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Train-throughput benchmark of the MI355X DeepSpeech2 hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: the headline and what
+follows from the timed steps alone.  --full adds every other leg after the timed steps: the deferred-readback and
+f32-GEMM legs, the data-parallel diagnostics and configs[3] (N > 1), inference, the per-kernel roofline and recurrence
+floor, the chain time share, the other BASELINE shapes, the loader leg, and the CPU oracle's baseline and parity check.
 
 A step = one full training pass over one minibatch of synthetic 16 kHz clips already resident in HBM:
 GPU log-spectrogram frontend -> conv/BiGRU/FC forward -> CTC -> backward -> (RCCL gradient all-reduce)
@@ -728,6 +733,10 @@ def main():
                     help='after the timed legs, replay the last DUMP_REPLAY_STEPS timed minibatches from the seeded starting state and '
                          'write what the last of them computed as DIR/<name>.npy (dump_outputs); '
                          'bench_outputs/ in the tree is git-ignored')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg (deferred readback, f32-GEMM leg, data-parallel '
+                         'diagnostics, inference, roofline and recurrence floor, chain time share, other shapes, loader, CPU '
+                         'baseline and parity); the --no-* switches above trim a --full run')
     args = ap.parse_args()
     if args.protocol == 'survey':
         args.warmup, args.steps = 20, 100
@@ -821,13 +830,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dt, frames, osteps, vsteps, pframes = float(tmax[0]), float(t[1]), float(t[2]), float(t[3]), float(t[4])
 
-    # the same steps as the product's own loop runs them: each step's readback deferred by one step
-    dt_defer, _, _ = timed_steps(lambda i: step(i + args.warmup), args.steps, 0, use_dist)
-    if use_dist:
-        ts = torch.tensor([dt_defer], dtype=torch.float64, device=dev)
-        dist.all_reduce(ts, op=dist.ReduceOp.MAX)
-        dt_defer = float(ts[0])
-    note('deferred-readback leg done: %.2f ms/step' % (1e3 * dt_defer / args.steps))
+    # every leg from here on but the dump runs under --full only.  The same steps as the product's own loop runs them: each
+    # step's readback deferred by one step
+    if args.full:
+        dt_defer, _, _ = timed_steps(lambda i: step(i + args.warmup), args.steps, 0, use_dist)
+        if use_dist:
+            ts = torch.tensor([dt_defer], dtype=torch.float64, device=dev)
+            dist.all_reduce(ts, op=dist.ReduceOp.MAX)
+            dt_defer = float(ts[0])
+        note('deferred-readback leg done: %.2f ms/step' % (1e3 * dt_defer / args.steps))
 
     # the same steps with every GEMM, conv2's forward pass and (B >= 17) the forward recurrence on the f32-input MFMA kernels
     # (ds2_gemm_split_mode 0, DS2_CONV_SPLIT=0, DS2_GRU_P2_BF16=0) instead of the default split-operand kernels on the bf16
@@ -836,7 +847,7 @@ def main():
     from ds2hip import ops as _ops
     gemm_mode = _ops.gemm_split_mode()
     dt_f32 = None
-    if gemm_mode != 0 and not args.no_f32_leg:
+    if args.full and gemm_mode != 0 and not args.no_f32_leg:
         _ops.gemm_split_mode(0)
         saved_env = {k: os.environ.get(k) for k in ('DS2_CONV_SPLIT', 'DS2_GRU_P2_BF16')}
         os.environ['DS2_CONV_SPLIT'] = '0'           # (read per call by the library: conv2 forward on the direct kernels,
@@ -859,7 +870,7 @@ def main():
     # data-parallel self-diagnosis (every rank takes part): what the collective costs alone, what the step costs with the
     # per-layer all-reduce overlapped with backward and without, and whether any recurrence launch fell back
     ddp = None
-    if use_dist:
+    if args.full and use_dist:
         from ds2hip import ops as _ops
         gflat = model.flat_grad()
         for _ in range(2):
@@ -900,7 +911,7 @@ def main():
 
     # BASELINE configs[3] at N > 1: 64 x 15 s over 8 GPUs = 8 clips of 15 s per rank (every rank, same barrier protocol)
     cfg3 = None
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         c3 = [make_resident(make_bin((7000 + rank * 10 + k, np.full(8, 15.0))), dev) for k in range(2)]
 
         def step3(i):
@@ -934,149 +945,157 @@ def main():
         return
 
     value = frames / dt
-
-    # secondary metric: inference = frontend + eval forward + greedy decode, same bins, rank 0 only
-    from codes.decoder import GreedyDecoder
-    decoder = GreedyDecoder(['_', ' ', "'"] + [chr(65 + i) for i in range(26)])
-    model.eval()
-    inf_frames, n_inf = 0, min(12, len(resident))
-    with torch.no_grad():
-        for rep in range(2):                         # pass 0 is the warm-up (every bin is a new shape for the allocator)
-            inf_frames = 0
-            torch.cuda.synchronize()
-            ti = time.time()
-            for i in range(n_inf):
-                inputs, pct = front(resident[i][0], resident[i][1])
-                probs = model(inputs)
-                sizes = (pct * probs.shape[1]).int()
-                decoder.decode(probs, sizes)
-                inf_frames += frames_of(mine[i])
-            torch.cuda.synchronize()
-            inf_dt = time.time() - ti
-    model.train()
     step_tflops = vsteps * TRAIN_FLOP_PER_OUT_STEP / dt / 1e12 / world           # per GPU, from the utterances' OWN steps
     step_tflops_padded = osteps * TRAIN_FLOP_PER_OUT_STEP / dt / 1e12 / world    # what was computed (bins padded to the longest)
-    t_mean = int(round(np.mean([out_steps_of(b) / len(b[0]) for b in mine])))
-    note('inference leg done')
-    roof = gru_pass_roofline(model, bsz, t_mean)
-    from codes.model import _BWD_SPARE_CUS
-    floor = None if args.no_floor else recurrence_floor(bsz, t_mean, model._rnn_hidden_size, dev, _BWD_SPARE_CUS)
-    gemm_roof = gemm_roofline(model, t_mean * bsz)
-    note('roofline legs done')
-    mean_bin = min(range(len(mine)), key=lambda i: abs(out_steps_of(mine[i]) / len(mine[i][0]) - t_mean))
-    share = chain_time_share(model, trainer, front, resident[mean_bin])
-    note('chain time share: %s' % json.dumps(share['phases_ms']))
+
     parity = None
-    if not args.no_cpu_baseline and world == 1 and args.fixed_seconds <= 0:
-        longest = max(range(len(plan)), key=lambda i: frames_of_plan(plan[i]))
-        parity = gpu_parity_side(model, trainer, front, decoder, plan[longest], dev)
-        parity['labels_txt'] = ['_', ' ', "'"] + [chr(65 + i) for i in range(26)]
-        note('parity leg (HIP side) done: loss_sum %.4f' % parity['loss_sum'])
-    ach, dur, flop = roof['bwd']
-    # HBM-side bytes per launch of the dominant kernel come from a SEPARATE rocprofv3 --pmc run of the same shape whose
-    # summary is committed under profiles/ (PMC collection cannot run inside this process); the file is named below
-    traffic, traffic_src, traffic_floor, traffic_alg = None, None, None, None
-    for name in ('r06_traffic.json', 'r05_traffic.json'):
-        try:
-            rec = json.load(open(os.path.join(ROOT, 'profiles', name)))
-            if rec['shape'] == {'T': t_mean, 'B': bsz, 'H': 800}:
-                traffic = rec['backward_recurrence_launch']['traffic_bytes_per_launch']
-                traffic_floor = rec['backward_recurrence_launch'].get('xcd_replicated_floor_bytes_per_launch')
-                traffic_alg = rec['backward_recurrence_launch'].get('algorithmic_hbm_bytes_per_launch')
-                traffic_src = 'profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/gru_step_timing.py, ' \
-                              'not measured in this run)' % name
-                break
-        except (OSError, KeyError, ValueError):
-            pass
+    if args.full:
+        # secondary metric: inference = frontend + eval forward + greedy decode, same bins, rank 0 only
+        from codes.decoder import GreedyDecoder
+        decoder = GreedyDecoder(['_', ' ', "'"] + [chr(65 + i) for i in range(26)])
+        model.eval()
+        inf_frames, n_inf = 0, min(12, len(resident))
+        with torch.no_grad():
+            for rep in range(2):                         # pass 0 is the warm-up (every bin is a new shape for the allocator)
+                inf_frames = 0
+                torch.cuda.synchronize()
+                ti = time.time()
+                for i in range(n_inf):
+                    inputs, pct = front(resident[i][0], resident[i][1])
+                    probs = model(inputs)
+                    sizes = (pct * probs.shape[1]).int()
+                    decoder.decode(probs, sizes)
+                    inf_frames += frames_of(mine[i])
+                torch.cuda.synchronize()
+                inf_dt = time.time() - ti
+        model.train()
+        t_mean = int(round(np.mean([out_steps_of(b) / len(b[0]) for b in mine])))
+        note('inference leg done')
+        roof = gru_pass_roofline(model, bsz, t_mean)
+        from codes.model import _BWD_SPARE_CUS
+        floor = None if args.no_floor else recurrence_floor(bsz, t_mean, model._rnn_hidden_size, dev, _BWD_SPARE_CUS)
+        gemm_roof = gemm_roofline(model, t_mean * bsz)
+        note('roofline legs done')
+        mean_bin = min(range(len(mine)), key=lambda i: abs(out_steps_of(mine[i]) / len(mine[i][0]) - t_mean))
+        share = chain_time_share(model, trainer, front, resident[mean_bin])
+        note('chain time share: %s' % json.dumps(share['phases_ms']))
+        if not args.no_cpu_baseline and world == 1 and args.fixed_seconds <= 0:
+            longest = max(range(len(plan)), key=lambda i: frames_of_plan(plan[i]))
+            parity = gpu_parity_side(model, trainer, front, decoder, plan[longest], dev)
+            parity['labels_txt'] = ['_', ' ', "'"] + [chr(65 + i) for i in range(26)]
+            note('parity leg (HIP side) done: loss_sum %.4f' % parity['loss_sum'])
+        ach, dur, flop = roof['bwd']
+        # HBM-side bytes per launch of the dominant kernel come from a SEPARATE rocprofv3 --pmc run of the same shape whose
+        # summary is committed under profiles/ (PMC collection cannot run inside this process); the file is named below
+        traffic, traffic_src, traffic_floor, traffic_alg = None, None, None, None
+        for name in ('r06_traffic.json', 'r05_traffic.json'):
+            try:
+                rec = json.load(open(os.path.join(ROOT, 'profiles', name)))
+                if rec['shape'] == {'T': t_mean, 'B': bsz, 'H': 800}:
+                    traffic = rec['backward_recurrence_launch']['traffic_bytes_per_launch']
+                    traffic_floor = rec['backward_recurrence_launch'].get('xcd_replicated_floor_bytes_per_launch')
+                    traffic_alg = rec['backward_recurrence_launch'].get('algorithmic_hbm_bytes_per_launch')
+                    traffic_src = 'profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/gru_step_timing.py, ' \
+                                  'not measured in this run)' % name
+                    break
+            except (OSError, KeyError, ValueError):
+                pass
     pct_of = lambda v, q: v[min(len(v) - 1, int(round(q * (len(v) - 1))))]          # noqa: E731
+    config = {'workload': 'BASELINE configs[1]: librispeech-from_scratch.json, 5xBiGRU-800 A=29, batch %d per GPU, '
+                          '16 kHz clips %s, full train step incl. GPU STFT frontend, CTC, clip+SGD'
+                          % (bsz, 'uniform 1-15 s in length-sorted bins' if args.fixed_seconds <= 0
+                             else 'all %.1f s long' % args.fixed_seconds),
+              'batch_per_gpu': bsz, 'global_batch': bsz * world, 'parallelism': 'dp%d' % world,
+              'last_loss': round(float(loss), 4),
+              'protocol': 'value / ms_per_step: a host synchronisation at the end of EVERY step (codes/engine.py:92, SURVEY.md '
+                          '8d); frames = valid spectrogram frames 1 + L // 160 of every clip (padding not counted)',
+              'protocol_name': args.protocol + (' (SURVEY.md 8d: 20 warm-up + 100 timed steps; median / p10 / p90 in '
+                                                'frames_per_s_per_step_rank0 and ms_per_step_rank0)' if args.protocol == 'survey'
+                                                else " (the driver's command line: --steps / --warmup as given)"),
+              'padded_frames_per_s': round(pframes / dt, 1),
+              'padding_note': 'a bin is padded to its longest clip (codes/data.py:132-152): B x T_max frames are computed per '
+                              'step, the valid ones are counted'}
+    if args.full:
+        config.update({
+            'deferred_readback': {'frames_per_s': round(frames / dt_defer, 1),
+                                  'ms_per_step': round(1e3 * dt_defer / args.steps, 3),
+                                  'note': 'the same steps as Trainer.run / train.py run them: each step\'s one readback '
+                                          'deferred by one step (round 3\'s headline)'},
+            'chain_time_share': share,
+            'gemm_arithmetic': {
+                'mode': gemm_mode,
+                'note': ('fp32 operands, fp32 accumulator, fp32 result; products on the bf16 matrix pipe after an '
+                         'error-free three-way split of every operand element (%d partial products, each exact; '
+                         'what is left out is below one fp32 rounding of the product: 2^-24.2 at most and 6e-9 rms over 1e6 random products, a '
+                         'correctly rounded fp32 multiply: 2^-24 and 2.5e-8): error against fp64 equal to the f32-input MFMA '
+                         'kernels\' (tests/test_kernels_gpu.py, tools/gemm_split_check.py)' % gemm_mode)
+                        if gemm_mode else 'f32-input MFMA kernels (v_mfma_f32_32x32x2_f32)',
+                'kernels_on_the_bf16_pipe': 'GEMMs, conv2 forward, forward recurrence from B = 17',
+                'same_steps_on_f32_input_mfma_gemms': None if dt_f32 is None else {
+                    'frames_per_s': round(frames / dt_f32, 1), 'ms_per_step': round(1e3 * dt_f32 / args.steps, 3),
+                    'note': 'deferred readback: compare with config.deferred_readback'}}})
+    config.update({
+        'persistent_to_step_fallbacks': (_fallbacks() if ddp is None
+                                         else ddp['persistent_to_step_fallbacks']),
+        'ms_per_step_rank0': {'median': round(1e3 * pct_of(per_sorted, 0.5), 3),
+                              'p10': round(1e3 * pct_of(per_sorted, 0.1), 3),
+                              'p90': round(1e3 * pct_of(per_sorted, 0.9), 3),
+                              'max': round(1e3 * per_sorted[-1], 3),
+                              'per_step': [round(1e3 * v, 2) for v in per],
+                              'allocator_growth_bytes_in_timed_region': int(reserved_growth)},
+        'frames_per_s_per_step_rank0': {'median': round(pct_of(step_rates, 0.5), 1),
+                                        'p10': round(pct_of(step_rates, 0.1), 1),
+                                        'p90': round(pct_of(step_rates, 0.9), 1)}})
+    # the whole-step figures follow from the timed steps alone; --full adds the per-kernel roofline around them
+    roofline = {'whole_step_tflops_per_gpu': round(step_tflops, 3),
+                'whole_step_frac_of_f32_mfma_peak': round(step_tflops / PEAK_F32_MFMA_TFLOPS, 5),
+                'whole_step_tflops_per_gpu_padded': round(step_tflops_padded, 3),
+                'whole_step_note': 'FLOP = 261.94 M x the utterances\' own output steps (valid frames); _padded counts the '
+                                   'steps computed (every clip padded to its bin\'s longest)'}
+    if args.full:
+        config['inference_frames_per_s_rank0'] = round(inf_frames / inf_dt, 1)
+        roofline = {'bound': 'latency' if bsz <= 16 else 'mfma',
+                    'bound_note': 'one launch = T dependent time steps; a step is a chain of three phases on every CU -- the '
+                                  'inter-CU hand-off of the new state through memory, the matrix phase at the fp32 MFMA rate '
+                                  'of the CUs it occupies, and the gate / reduction skeleton (DESIGN.md section 6).  achieved / '
+                                  'peak / frac price the launch against the fp32-input MFMA roof (the contract\'s yardstick); '
+                                  'floor_us_per_step is what the latency model allows',
+                    'kernel': 'the backward recurrence launch: gru_bwd_persistent6_kernel<25, 7> (d(h) hand-off, 28 units per workgroup) '
+                              'under the layers below the top one, <25, 5> (20 units) under the top layer (one launch = all T=%d steps '
+                              'of a BiGRU layer, both directions, B=%d)' % (t_mean, bsz),
+                    'achieved': round(ach, 3), 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': round(ach / PEAK_F32_MFMA_TFLOPS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
+                    'traffic_algorithmic': traffic_alg,
+                    'traffic_floor_of_an_exchange_through_memory': traffic_floor,
+                    'traffic_note': 'bytes at the memory side per launch (2 x FETCH_SIZE + WRITE_SIZE).  traffic_algorithmic: the saved '
+                                    'activations once (an exchange that stayed on chip would move nothing else).  An exchange through memory '
+                                    'between CUs on EIGHT XCDs with non-coherent L2s cannot go below the payload fetched once into '
+                                    'EVERY XCD (traffic_floor_...): the ratio to that, not to the algorithmic bytes, is the waste',
+                    'avg_launch_us': round(dur * 1e6, 1), 'us_per_time_step': round(dur * 1e6 / t_mean, 3),
+                    'floor_us_per_step': floor,
+                    'flop_per_launch': flop,
+                    'launch_forms_us': {
+                        'top layer (nothing queued beside it: the widest grid)': round(roof['bwd_top'][1] * 1e6, 1),
+                        'layers below (CUs left to the weight-gradient GEMMs of the layer above)': round(roof['bwd_below'][1] * 1e6, 1),
+                        'note': 'avg_launch_us = the mean launch of a step (1 : num_layers - 1), each form timed stand-alone; '
+                                'ds2_gru_bidir_bwd_persistent_ex, include/ds2hip.h'},
+                    'fwd_kernel_tflops': round(roof['fwd'][0], 3),
+                    'fwd_us_per_time_step': round(roof['fwd'][1] * 1e6 / t_mean, 3),
+                    **roofline,
+                    'gemm': gemm_roof}
     result = {
         'metric': 'train frames/sec, DeepSpeech2 5xBiGRU-800',
         'value': round(value, 1), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': round(1e3 * dt / args.steps, 3), 'higher_is_better': True, 'scaling': 'weak',
         'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': 'BASELINE configs[1]: librispeech-from_scratch.json, 5xBiGRU-800 A=29, batch %d per GPU, '
-                               '16 kHz clips %s, full train step incl. GPU STFT frontend, CTC, clip+SGD'
-                               % (bsz, 'uniform 1-15 s in length-sorted bins' if args.fixed_seconds <= 0
-                                  else 'all %.1f s long' % args.fixed_seconds),
-                   'batch_per_gpu': bsz, 'global_batch': bsz * world, 'parallelism': 'dp%d' % world,
-                   'last_loss': round(float(loss), 4),
-                   'protocol': 'value / ms_per_step: a host synchronisation at the end of EVERY step (codes/engine.py:92, SURVEY.md '
-                               '8d); frames = valid spectrogram frames 1 + L // 160 of every clip (padding not counted)',
-                   'protocol_name': args.protocol + (' (SURVEY.md 8d: 20 warm-up + 100 timed steps; median / p10 / p90 in '
-                                                     'frames_per_s_per_step_rank0 and ms_per_step_rank0)' if args.protocol == 'survey'
-                                                     else " (the driver's command line: --steps / --warmup as given)"),
-                   'padded_frames_per_s': round(pframes / dt, 1),
-                   'padding_note': 'a bin is padded to its longest clip (codes/data.py:132-152): B x T_max frames are computed per '
-                                   'step, the valid ones are counted',
-                   'deferred_readback': {'frames_per_s': round(frames / dt_defer, 1),
-                                         'ms_per_step': round(1e3 * dt_defer / args.steps, 3),
-                                         'note': 'the same steps as Trainer.run / train.py run them: each step\'s one readback '
-                                                 'deferred by one step (round 3\'s headline)'},
-                   'chain_time_share': share,
-                   'gemm_arithmetic': {
-                       'mode': gemm_mode,
-                       'note': ('fp32 operands, fp32 accumulator, fp32 result; products on the bf16 matrix pipe after an '
-                                'error-free three-way split of every operand element (%d partial products, each exact; '
-                                'what is left out is below one fp32 rounding of the product: 2^-24.2 at most and 6e-9 rms over 1e6 random products, a '
-                                'correctly rounded fp32 multiply: 2^-24 and 2.5e-8): error against fp64 equal to the f32-input MFMA '
-                                'kernels\' (tests/test_kernels_gpu.py, tools/gemm_split_check.py)' % gemm_mode)
-                               if gemm_mode else 'f32-input MFMA kernels (v_mfma_f32_32x32x2_f32)',
-                       'kernels_on_the_bf16_pipe': 'GEMMs, conv2 forward, forward recurrence from B = 17',
-                       'same_steps_on_f32_input_mfma_gemms': None if dt_f32 is None else {
-                           'frames_per_s': round(frames / dt_f32, 1), 'ms_per_step': round(1e3 * dt_f32 / args.steps, 3),
-                           'note': 'deferred readback: compare with config.deferred_readback'}},
-                   'persistent_to_step_fallbacks': (_fallbacks() if ddp is None
-                                                    else ddp['persistent_to_step_fallbacks']),
-                   'ms_per_step_rank0': {'median': round(1e3 * pct_of(per_sorted, 0.5), 3),
-                                         'p10': round(1e3 * pct_of(per_sorted, 0.1), 3),
-                                         'p90': round(1e3 * pct_of(per_sorted, 0.9), 3),
-                                         'max': round(1e3 * per_sorted[-1], 3),
-                                         'per_step': [round(1e3 * v, 2) for v in per],
-                                         'allocator_growth_bytes_in_timed_region': int(reserved_growth)},
-                   'frames_per_s_per_step_rank0': {'median': round(pct_of(step_rates, 0.5), 1),
-                                                   'p10': round(pct_of(step_rates, 0.1), 1),
-                                                   'p90': round(pct_of(step_rates, 0.9), 1)},
-                   'inference_frames_per_s_rank0': round(inf_frames / inf_dt, 1)},
-        'roofline': {'bound': 'latency' if bsz <= 16 else 'mfma',
-                     'bound_note': 'one launch = T dependent time steps; a step is a chain of three phases on every CU -- the '
-                                   'inter-CU hand-off of the new state through memory, the matrix phase at the fp32 MFMA rate '
-                                   'of the CUs it occupies, and the gate / reduction skeleton (DESIGN.md section 6).  achieved / '
-                                   'peak / frac price the launch against the fp32-input MFMA roof (the contract\'s yardstick); '
-                                   'floor_us_per_step is what the latency model allows',
-                     'kernel': 'the backward recurrence launch: gru_bwd_persistent6_kernel<25, 7> (d(h) hand-off, 28 units per workgroup) '
-                               'under the layers below the top one, <25, 5> (20 units) under the top layer (one launch = all T=%d steps '
-                               'of a BiGRU layer, both directions, B=%d)' % (t_mean, bsz),
-                     'achieved': round(ach, 3), 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': round(ach / PEAK_F32_MFMA_TFLOPS, 5), 'traffic': traffic, 'traffic_source': traffic_src,
-                     'traffic_algorithmic': traffic_alg,
-                     'traffic_floor_of_an_exchange_through_memory': traffic_floor,
-                     'traffic_note': 'bytes at the memory side per launch (2 x FETCH_SIZE + WRITE_SIZE).  traffic_algorithmic: the saved '
-                                     'activations once (an exchange that stayed on chip would move nothing else).  An exchange through memory '
-                                     'between CUs on EIGHT XCDs with non-coherent L2s cannot go below the payload fetched once into '
-                                     'EVERY XCD (traffic_floor_...): the ratio to that, not to the algorithmic bytes, is the waste',
-                     'avg_launch_us': round(dur * 1e6, 1), 'us_per_time_step': round(dur * 1e6 / t_mean, 3),
-                     'floor_us_per_step': floor,
-                     'flop_per_launch': flop,
-                     'launch_forms_us': {
-                         'top layer (nothing queued beside it: the widest grid)': round(roof['bwd_top'][1] * 1e6, 1),
-                         'layers below (CUs left to the weight-gradient GEMMs of the layer above)': round(roof['bwd_below'][1] * 1e6, 1),
-                         'note': 'avg_launch_us = the mean launch of a step (1 : num_layers - 1), each form timed stand-alone; '
-                                 'ds2_gru_bidir_bwd_persistent_ex, include/ds2hip.h'},
-                     'fwd_kernel_tflops': round(roof['fwd'][0], 3),
-                     'fwd_us_per_time_step': round(roof['fwd'][1] * 1e6 / t_mean, 3),
-                     'whole_step_tflops_per_gpu': round(step_tflops, 3),
-                     'whole_step_frac_of_f32_mfma_peak': round(step_tflops / PEAK_F32_MFMA_TFLOPS, 5),
-                     'whole_step_tflops_per_gpu_padded': round(step_tflops_padded, 3),
-                     'whole_step_note': 'FLOP = 261.94 M x the utterances\' own output steps (valid frames); _padded counts the '
-                                        'steps computed (every clip padded to its bin\'s longest)',
-                     'gemm': gemm_roof},
+        'config': config, 'roofline': roofline,
     }
     if cfg3 is not None:
         result['config']['config3'] = cfg3
     if ddp is not None:
         ddp['environment'] = dp_env          # queue / channel settings and the CPU placement applied (codes/utils/dist_utils.py)
         result['config']['data_parallel'] = ddp
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # the other single-GPU BASELINE shapes on the same model, a few steps each
         p32 = bin_plan(32, 8, seed=43)                      # a length-sorted corpus cut into bins of 32, as BucketingSampler does
         result['config']['other_shapes'] = {
@@ -1087,7 +1106,7 @@ def main():
         note('other shapes done')
         result['config']['loader'] = loader_leg(trainer, plan, dev)
         note('loader leg done')
-    if not args.no_cpu_baseline and world == 1:      # the CPU oracle is timed beside the GPU at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:      # the CPU oracle is timed beside the GPU at N = 1 only
         result['cpu_baseline'] = cpu_baseline(plan, budget_s=args.cpu_budget_s, full=not args.cpu_quick, parity=parity)
         if 'parity_vs_cpu_oracle' in result['cpu_baseline']:
             result['parity_vs_cpu_oracle'] = result['cpu_baseline'].pop('parity_vs_cpu_oracle')

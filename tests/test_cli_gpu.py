@@ -260,3 +260,29 @@ def test_freeze_config_cli_from_an_en_checkpoint(tmp_path):
         buf = state.get(i, {}).get('momentum_buffer')
         assert buf is None or not bool(buf.any())
     assert bool(state[params[8]]['momentum_buffer'].any())
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the headline and what follows from the
+    timed steps, --dump-outputs written, none of the legs that --full adds (they are after the timed steps and take runs of
+    their own: deferred readback, f32-GEMM leg, inference, roofline, chain time share, other shapes, loader, CPU oracle)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path / 'dump')],
+                         capture_output=True, text=True, env=dict(os.environ), timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, out.stdout[-3000:]
+    res = json.loads(lines[0])
+    assert res['metric'] == 'train frames/sec, DeepSpeech2 5xBiGRU-800' and res['unit'] == 'frames/s'
+    assert res['higher_is_better'] is True and res['dtype'] == 'f32' and (res['steps'], res['warmup']) == (3, 1)
+    assert res['value'] > 0 and res['ms_per_step'] > 0
+    assert res['config']['persistent_to_step_fallbacks'] == 0
+    assert len(res['config']['ms_per_step_rank0']['per_step']) == 3
+    for key in ('deferred_readback', 'gemm_arithmetic', 'chain_time_share', 'inference_frames_per_s_rank0', 'other_shapes',
+                'loader', 'data_parallel', 'config3'):
+        assert key not in res['config'], key
+    assert 'cpu_baseline' not in res and 'parity_vs_cpu_oracle' not in res
+    assert sorted(res['roofline']) == ['whole_step_frac_of_f32_mfma_peak', 'whole_step_note', 'whole_step_tflops_per_gpu',
+                                       'whole_step_tflops_per_gpu_padded']
+    assert (tmp_path / 'dump' / 'loss.npy').exists() and (tmp_path / 'dump' / 'params_sample.npy').exists()
+    assert 'deferred-readback leg' not in out.stderr and 'cpu baseline' not in out.stderr

@@ -1,8 +1,8 @@
 # Round-6 soak + survey-protocol line (run on the GPU box from the repo root; outputs under gpurun_out/final_r06/)
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/final_r06; rm -rf $OUT; mkdir -p $OUT
-timeout 600 python3 bench.py --protocol survey --no-cpu-baseline --no-extras > $OUT/survey_protocol.json 2> $OUT/survey.err
-run() { name=$1; shift; timeout 900 python3 bench.py --no-extras --no-cpu-baseline --no-floor "$@" > $OUT/$name.json 2> $OUT/$name.err; python3 - $OUT/$name.json "$name" "$*" <<'PY'
+timeout 600 python3 bench.py --protocol survey --full --no-cpu-baseline --no-extras > $OUT/survey_protocol.json 2> $OUT/survey.err
+run() { name=$1; shift; timeout 900 python3 bench.py --full --no-extras --no-cpu-baseline --no-floor "$@" > $OUT/$name.json 2> $OUT/$name.err; python3 - $OUT/$name.json "$name" "$*" <<'PY'
 import json, sys
 r = json.load(open(sys.argv[1]))
 c = r['config']

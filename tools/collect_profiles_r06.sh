@@ -3,7 +3,7 @@
 # off, so the kernel-stats CSVs contain product launches only.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/prof_r06; rm -rf $OUT; mkdir -p $OUT
-B="--no-cpu-baseline --no-extras --no-floor --no-f32-leg"
+B="--full --no-cpu-baseline --no-extras --no-floor --no-f32-leg"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/b10 -- python3 bench.py --steps 24 --warmup 0 $B > $OUT/b10.json 2> $OUT/b10.err
 python3 tools/step_idle_gaps.py $OUT/b10/*/*kernel_trace.csv > $OUT/b10_idle_gaps.txt 2>&1
 if [ "$1" != "quick" ]; then

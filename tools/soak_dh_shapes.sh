@@ -1,6 +1,6 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/soak_r06b; rm -rf $OUT; mkdir -p $OUT
-run() { name=$1; shift; timeout 1500 python3 bench.py --no-extras --no-cpu-baseline --no-floor --no-f32-leg "$@" > $OUT/$name.json 2> $OUT/$name.err; python3 - $OUT/$name.json "$name" "$*" <<'PY'
+run() { name=$1; shift; timeout 1500 python3 bench.py --full --no-extras --no-cpu-baseline --no-floor --no-f32-leg "$@" > $OUT/$name.json 2> $OUT/$name.err; python3 - $OUT/$name.json "$name" "$*" <<'PY'
 import json, sys
 r = json.load(open(sys.argv[1])); c = r['config']
 print('%-12s %-36s sync %9.1f frames/s %7.3f ms | deferred %9.1f %7.3f ms | fall-backs %s | loss %s'
