@@ -1951,7 +1951,7 @@ __global__ __launch_bounds__(NWP * 64) void gru_fwd_persistent5_kernel(float* __
             // front of the NEXT step's first-attempt sleep, which only has to shrink by as much -- but that sleep adapts by one
             // s_sleep per 2^k clean steps: with the launch's usual start (8 sleeps, k = 6) the planes cost 0.10 us per step
             // whichever half of them (the arithmetic, the store) was compiled in; started at 3 sleeps they cost 0.01
-            // (launch_fwd_persistent5).
+            // (fwd_plan).
             if (coef) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (mine) {
@@ -1986,7 +1986,9 @@ __global__ __launch_bounds__(NWP * 64) void gru_fwd_persistent5_kernel(float* __
 // -> 2.14 / 2.09 / 2.14 (a fixed delay of 6-8 sleeps without adaptation: 2.09-2.10) -- with the fast decay the delay creeps
 // down until a wave re-loads (17 % of wave-steps did), and a re-load costs this kernel more than a few sleeps too many; the
 // older kernels (B = 4 / 8) lose with the slow decay (forward 1.65 -> 1.75 / backward 2.32 -> 2.50) and keep (1, 2).
-inline int spec_timing(int bwd, int def_delay = -1, int def_inc = 1, int def_log2clean = 2) {
+// knob: the kernel's own "delay,inc,log2clean" override of those defaults (DS2_GRU_FWD4_SPEC, ..., for A/B runs).
+inline int spec_timing(int bwd, const char* knob = nullptr, int def_delay = -1, int def_inc = 1, int def_log2clean = 2) {
+    if (const char* e = knob ? ds2_tune_env(knob) : nullptr) sscanf(e, "%d,%d,%d", &def_delay, &def_inc, &def_log2clean);
     int delay = def_delay >= 0 ? def_delay : (bwd ? 14 : 10), backoff = 2;
     const char* e = ds2_tune_env(bwd ? "DS2_GRU_SPEC_BWD" : "DS2_GRU_SPEC_FWD");
     if (e) {
@@ -2024,152 +2026,6 @@ inline int kbal_kpl(int H, int rows_per_part, int proto) {
     return kpl;
 }
 
-template <int P, int NBT, int PROTO, int UGX = 0>
-bool launch_fwd_persistent4(float* G, float* ghn, float* hout, const float* w_hh, SyncWs* sync, float* ring, int T, int B,
-                            int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 3};
-    const int ngi = pick_kbw(ds2_cdiv(ds2_cdiv(H, 64), NWP), opts, 3);
-    constexpr int UNITS = UGX ? 4 * UGX : 8 * P;
-    dim3 grid(ds2_cdiv(H, UNITS), 2, P), block(NWP * 64);
-    const int ncg = (ds2_cdiv(B, P) + 3) / 4;
-    const size_t lds = (size_t)ncg * 4 * 3 * UNITS * FWD4_PITCH * sizeof(float);
-    // k-balanced deal: built for H = 800 (KPL = 25), the BASELINE configs' width, in the forms without a B set
-    if constexpr (PROTO != 0 && NBT == 1 && ((UGX ? 3 * UGX : 6 * P) % 4 != 2)) {
-        if (kbal_kpl(H, ds2_cdiv(B, P), PROTO) == 25) {
-            auto kern = &gru_fwd_persistent4_kernel<1, P, NBT, PROTO, UGX, 25>;
-            if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return false;
-            if (!grid_is_coresident(kern, grid, lds)) return false;
-            // (this kernel's hand-off timing: DS2_GRU_FWD4_SPEC = "delay,inc,log2clean" for A/B runs)
-            // (measured, us per forward step, (10, 1, 2) -> (8, 1, 5): B = 8 2.15 -> 2.05, B = 6 1.97 -> 1.94, B = 5 1.99 -> 1.94)
-            int d = 8, inc = 1, l2c = 5;
-            if (const char* e = ds2_tune_env("DS2_GRU_FWD4_SPEC")) sscanf(e, "%d,%d,%d", &d, &inc, &l2c);
-            hipLaunchKernelGGL(kern, grid, block, lds, st, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, spec_timing(0, d, inc, l2c));
-            return true;
-        }
-    }
-#define DS2_FWD4_CASE(K)                                                                                         \
-    case K:                                                                                                      \
-        if (lds > 64 * 1024 &&                                                                                   \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_fwd_persistent4_kernel<K, P, NBT, PROTO, UGX>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)             \
-            return false;                                                                                        \
-        if (!grid_is_coresident(&gru_fwd_persistent4_kernel<K, P, NBT, PROTO, UGX>, grid, lds)) return false;                \
-        hipLaunchKernelGGL((gru_fwd_persistent4_kernel<K, P, NBT, PROTO, UGX>), grid, block, lds, st, G, ghn, hout, w_hh, sync,    \
-                           ring, T, B, H, dbg, spec_timing(0));                                                                  \
-        return true;
-    switch (ngi) {
-        DS2_FWD4_CASE(1)
-        DS2_FWD4_CASE(2)
-        DS2_FWD4_CASE(3)
-    }
-#undef DS2_FWD4_CASE
-    return false;
-}
-
-// the row deal (gru_fwd_persistent5_kernel): three batch parts of one quad each, 20 units per workgroup, H = 8 KW
-template <int KW, int P = 3>
-bool launch_fwd_persistent5(float* G, float* ghn, float* hout, const float* w_hh, float* coef, SyncWs* sync, float* ring, int T,
-                            int B, int H, int dbg, hipStream_t st) {
-    constexpr int UNITS = 20;
-    dim3 grid(ds2_cdiv(H, UNITS), 2, P), block(NWP * 64);
-    auto kern = &gru_fwd_persistent5_kernel<KW, UNITS, P>;
-    if (!grid_is_coresident(kern, grid, 0)) return false;
-    // (first-attempt delay and adaptation policy of THIS kernel: DS2_GRU_FWD5_SPEC = "delay,inc,log2clean" for A/B runs)
-    // With the coefficient planes as an output (a training pass whose backward recurrence hands off dh) a step has more work
-    // behind its payload store and wants a shorter sleep from the start -- measured at B = 10 / 9, us per forward step with the
-    // planes, (8, 1, 6) -> (3, 1, 5): 2.27 / 2.16 -> 2.16 / 2.08 (without the planes: 2.15 at B = 10 either way); B = 12 (three full
-    // quads) is the exception: 2.32 -> 2.48
-    int d = 8, inc = 1, l2c = 6;
-    if (B <= 11) d = 3, l2c = 5;                    // (without the planes: 2.18 -> 2.15 at B = 10)
-    if (const char* e = ds2_tune_env("DS2_GRU_FWD5_SPEC")) sscanf(e, "%d,%d,%d", &d, &inc, &l2c);
-    hipLaunchKernelGGL(kern, grid, block, 0, st, G, ghn, hout, w_hh, coef, sync, ring, T, B, H, dbg, spec_timing(0, d, inc, l2c));
-    return true;
-}
-
-template <int NRG, int PROTO, int NP = NRG / 2>
-bool launch_bwd_persistent4(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
-                            SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 3, 5};
-    const int ngi = pick_kbw(ds2_cdiv(ds2_cdiv(3 * H, 64), NWP), opts, 4);
-    constexpr int NPART = NP;
-    dim3 grid(ds2_cdiv(H, 4 * NRG), 2, NPART), block(NWP * 64);
-    const int ncg = (ds2_cdiv(B, NPART) + 3) / 4;
-    const size_t lds = (size_t)NRG * ncg * 16 * RED4_PITCH * sizeof(float);
-#define DS2_BWD4_CASE(K)                                                                                         \
-    case K:                                                                                                      \
-        if (lds > 64 * 1024 &&                                                                                   \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_persistent4_kernel<K, NRG, PROTO, NP>),              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)             \
-            return false;                                                                                        \
-        if (!grid_is_coresident(&gru_bwd_persistent4_kernel<K, NRG, PROTO, NP>, grid, lds)) return false;                   \
-        hipLaunchKernelGGL((gru_bwd_persistent4_kernel<K, NRG, PROTO, NP>), grid, block, lds, st, G, ghn, hout, d_out, w_hh_t,    \
-                           sync, ring, T, B, H, dbg, spec_timing(1));                                                            \
-        return true;
-    switch (ngi) {
-        DS2_BWD4_CASE(1)
-        DS2_BWD4_CASE(2)
-        DS2_BWD4_CASE(3)
-        DS2_BWD4_CASE(5)
-    }
-#undef DS2_BWD4_CASE
-    return false;
-}
-
-// the broadcast deal (gru_bwd_persistent5_kernel): three batch parts of one quad each, speculative hand-off
-template <int NRG, int NPART = 3>
-bool launch_bwd_persistent5(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
-                            SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 3, 5};
-    const int ngi = pick_kbw(ds2_cdiv(ds2_cdiv(3 * H, 64), NWP), opts, 4);
-    dim3 grid(ds2_cdiv(H, 4 * NRG), 2, NPART), block(NWP * 64);
-    // (first-attempt delay and adaptation policy of THIS kernel: DS2_GRU_BWD5_SPEC = "delay,inc,log2clean" for A/B runs)
-    // (measured at B = 10, us per step, (14, 1, 2) -> (10, 1, 4): 28 units 2.95 -> 2.86, 24 units 2.74 -> 2.65; 20 units
-    // 2.67-2.69 -> 2.54, and 2.51 with (10, 1, 5) -- with that the broadcast deal beats the 16-k-blocks deal's 2.61-2.64 there too)
-    int d = NRG == 4 ? 8 : 10, inc = 1, l2c = NRG <= 5 ? 5 : 4;
-    if (const char* e = ds2_tune_env("DS2_GRU_BWD5_SPEC")) sscanf(e, "%d,%d,%d", &d, &inc, &l2c);
-    const int spec = spec_timing(1, d, inc, l2c);
-#define DS2_BWD5_CASE(K)                                                                                         \
-    case K:                                                                                                      \
-        if (!grid_is_coresident(&gru_bwd_persistent5_kernel<K, NRG, NPART>, grid, 0)) return false;              \
-        hipLaunchKernelGGL((gru_bwd_persistent5_kernel<K, NRG, NPART>), grid, block, 0, st, G, ghn, hout, d_out, w_hh_t, sync, ring, \
-                           T, B, H, dbg, spec);                                                                  \
-        return true;
-    switch (ngi) {
-        DS2_BWD5_CASE(1)
-        DS2_BWD5_CASE(2)
-        DS2_BWD5_CASE(3)
-        DS2_BWD5_CASE(5)
-    }
-#undef DS2_BWD5_CASE
-    return false;
-}
-
-// the d(h) hand-off (gru_bwd_persistent6_kernel): H = 32 RPW, one batch quad per part, speculative hand-off
-template <int RPW, int NRG, int NPART = 3>
-bool launch_bwd_persistent6(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t, const float* coef,
-                            SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    dim3 grid(ds2_cdiv(H, 4 * NRG), 2, NPART), block(NWP * 64);
-    auto kern = &gru_bwd_persistent6_kernel<RPW, NRG, NPART>;
-#if defined(DS2_TIMING) || defined(DS2_FAULT_INJECT)
-    // the ablated instantiations bench.py's floor leg and the timing tools ask for (the forms of a B = 9 .. 12 step at H = 800)
-    if constexpr (RPW == 25 && NPART == 3 && (NRG == 5 || NRG == 7)) {
-        const int abl = dbg & (2 | 2048 | 4096 | 8192);
-        if (abl == (2 | 8192) || abl == 2) kern = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 2 | 8192>;
-        else if (abl == (2048 | 8192) || abl == 2048) kern = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 2048 | 8192>;
-        else if (abl == (4096 | 8192) || abl == 4096) kern = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 4096 | 8192>;
-    }
-#endif
-    if (!grid_is_coresident(kern, grid, 0)) return false;
-    // (first-attempt delay and adaptation policy of THIS kernel: DS2_GRU_BWD6_SPEC = "delay,inc,log2clean" for A/B runs)
-    int d = 8, inc = 1, l2c = 5;
-    if (const char* e = ds2_tune_env("DS2_GRU_BWD6_SPEC")) sscanf(e, "%d,%d,%d", &d, &inc, &l2c);
-    hipLaunchKernelGGL(kern, grid, block, 0, st, G, ghn, hout, d_out, w_hh_t, coef, sync, ring, T, B, H, dbg,
-                       spec_timing(1, d, inc, l2c));
-    return true;
-}
-
 inline bool persistent_ok(int B, int H) {
     return (H % 16 == 0) && (2 * ds2_cdiv(H, PJU) <= max_persistent_wgs()) && (B <= 64) &&
            (ds2_cdiv(3 * H / 16, NWP) <= 19) && (ds2_cdiv(H / 16, NWP) <= 7);
@@ -2179,10 +2035,10 @@ inline bool persistent_ok(int B, int H) {
 // Default by the batch rows a workgroup handles: ONE batch quad (<= 4 rows: B <= 12 with three parts) -> speculative
 // (B = 10: 3.45 -> 3.1 us per step, B = 8: 2.9 -> 2.5, B = 4: 2.5 -> 1.9); with more rows the step is MFMA / store bound, the
 // canaries double the write-through stores and the drained protocol is faster (B = 32 backward: 6.4 vs 6.8 us, B = 64:
-// 11.3 vs 12.8).  DS2_GRU_PROTO = 0 / 2 forces one (A/B timing).
+// 11.3 vs 12.8).  DS2_GRU_PROTO = 0 / 2 forces one (A/B timing; 1 counts as 2).
 inline int handoff_protocol(int rows_per_part) {
     const char* e = ds2_tune_env("DS2_GRU_PROTO");
-    if (e && e[0] >= '0' && e[0] <= '2') return e[0] - '0';
+    if (e && e[0] >= '0' && e[0] <= '2') return e[0] == '0' ? 0 : 2;
     return rows_per_part <= 4 ? 2 : 0;
 }
 
@@ -2200,12 +2056,6 @@ inline int dbg_flags() {
 #endif
 }
 
-}  // namespace
-
-// A data-tagged-granule hand-off (Guideline 16 R2: every consumer wave polls the 8-byte {value, epoch} granules it
-// needs) was built and measured in round 1: correct, but 1.5x (forward) to 2.1x (backward) SLOWER per step than the
-// counter form -- 1600 waves polling payload lines swamp the fabric ("polling-cost" row of the price list).
-// exchange ring: [dir 2][slot 2][batch tiles][k blocks of 16][16][16] floats, sized for the backward pass (K = 3H)
 // DS2_GRU_P2_BF16 = 0 / 1: the two-part forms on the f32-input MFMA or on the bf16 pipe with split operands (default where
 // H % 32 == 0 and a wave holds at most four forward k blocks of 32, i.e. H <= 1024)
 inline bool p2_bf16(int H) {
@@ -2213,6 +2063,247 @@ inline bool p2_bf16(int H) {
     if (e && e[0] == '0') return false;
     return H % 32 == 0 && H <= 1024;
 }
+
+// ---- form selection: which kernel a launch runs, decided before anything is launched --------------------------------------
+enum GruForm : int {
+    FORM_4X4,     // the 4x4x1 forms in k groups: gru_fwd_persistent4_kernel / gru_bwd_persistent4_kernel
+    FORM_KBAL,    // forward: the k-balanced deal of gru_fwd_persistent4_kernel (KPL = 25, H = 800)
+    FORM_ROWS,    // forward: the row deal (gru_fwd_persistent5_kernel), writes the coefficient planes itself
+    FORM_BCAST,   // backward: the broadcast deal (gru_bwd_persistent5_kernel)
+    FORM_DH,      // backward: the d(h) hand-off (gru_bwd_persistent6_kernel)
+    FORM_16,      // the 16x16 forms of gru_persist16.hip (ds2_p16_launch_*): FORM_16 + its form number
+    FORM_16P2,
+    FORM_16P2B,
+};
+struct GruPlan {
+    int form;     // GruForm
+    int parts;    // batch parts (grid z; the 16x16 forms: 1 or 2)
+    int tiles;    // 4x4x1 forward: batch-row passes per workgroup (NBT); 16x16 forms: batch tiles of 16 per workgroup
+    int proto;    // hand-off protocol of the 4x4x1 forms (0 counted, 2 speculative)
+    int units;    // hidden units per workgroup (4x4x1 forms; the backward row groups are units / 4)
+    int spec;     // spec_timing() word (speculative forms)
+};
+
+// The 16x16 forms.  p2: two batch parts of one or two tiles of 16 -- on the bf16 pipe with split operands or on the f32-input
+// MFMA; otherwise the whole batch per workgroup in one, two or four tiles.
+inline GruPlan plan16(int B, bool p2, bool bf16) {
+    if (p2) return {bf16 ? FORM_16P2B : FORM_16P2, 2, (B + 1) / 2 <= 16 ? 1 : 2, 0, 0, 0};
+    return {FORM_16, 1, B <= 16 ? 1 : (B <= 32 ? 2 : 4), 0, 0, 0};
+}
+
+// Form by batch size.  Measured (H = 800, us per step, 4x4x1 broadcast form with the whole batch per workgroup vs 16x16x4
+// form): B=4 2.57 / 3.65, B=10 3.84 / 3.88, B=16 4.41 / 3.89, B=32 7.44 / 5.56 -- the 4x4x1 form's cost grows with every batch
+// quad (and, with batch parts, with quads x parts for the MFMAs but only quads for the loads), the 16x16x4 form's with every
+// tile of 16.  DS2_GRU_FWD = "4" / "16" forces a form, DS2_GRU_FWD_SPLIT = 1 / 2 / 3 the number of batch parts (A/B timing).
+inline GruPlan fwd_plan(int B, int H, int max_wgs) {
+    const char* form = getenv("DS2_GRU_FWD");
+    int parts = B <= 4 ? 1 : (B <= 8 ? 2 : 3);
+    const char* split = ds2_tune_env("DS2_GRU_FWD_SPLIT");
+    if (split && split[0] >= '1' && split[0] <= '3') parts = split[0] - '0';
+    if (parts > B) parts = B;
+    // gate-role capacity: two passes of 512 / (4 * 8 parts) batch rows per workgroup; all workgroups co-resident
+    while (parts < 3 && ds2_cdiv(B, parts) > 2 * (NWP * 64 / (32 * parts))) ++parts;
+    if (2 * ds2_cdiv(H, 8 * parts) * parts > max_wgs) parts = 1;
+    const int bper = ds2_cdiv(B, parts), rpp = NWP * 64 / (32 * parts);
+    const bool fits4 = ds2_cdiv(ds2_cdiv(H, 64), NWP) <= 3 && bper <= 2 * rpp &&
+                       (size_t)((bper + 3) / 4) * 4 * 24 * parts * FWD4_PITCH * 4 <= 140 * 1024;
+    if ((form ? form[0] == '4' : B <= 12) && fits4) {
+        GruPlan p = {FORM_4X4, parts, bper > rpp ? 2 : 1, handoff_protocol(bper), 8 * parts, spec_timing(0)};
+        // three parts, one batch quad each, speculative hand-off (B = 9 .. 12): 20-unit slices on 240 CUs when they fit
+        // (the row deal with two batch parts -- 20 units, 160 workgroups -- measured at B = 8: 2.30 us per step against 2.15 for
+        // the 16-unit k-balanced form on 200: its 48 gate rows fill 12 of the 16 blocks, the row deal would issue 100 MFMAs for 75)
+        const char* wide = getenv("DS2_GRU_FWD_WIDE");
+        if (parts == 3 && p.tiles == 1 && p.proto != 0 && (wide ? wide[0] == '1' : true) && H % 4 == 0 &&
+            6 * ds2_cdiv(H, 20) <= max_wgs && 6 * ds2_cdiv(H, 20) > 6 * ds2_cdiv(H, 24)) {
+            p.units = 20;
+            // the row deal where it is built (H = 800: 100 columns per wave); DS2_GRU_FWD_ROWS = 0: the k-balanced deal (A/B timing)
+            const char* rows = ds2_tune_env("DS2_GRU_FWD_ROWS");
+            if (H == 800 && bper <= 4 && !(rows && rows[0] == '0')) {
+                p.form = FORM_ROWS;
+                // With the coefficient planes as an output (a training pass whose backward recurrence hands off dh) a step has
+                // more work behind its payload store and wants a shorter sleep from the start -- measured at B = 10 / 9, us per
+                // forward step with the planes, (8, 1, 6) -> (3, 1, 5): 2.27 / 2.16 -> 2.16 / 2.08 (without the planes: 2.15 at
+                // B = 10 either way; 2.18 -> 2.15 at B = 10); B = 12 (three full quads) is the exception: 2.32 -> 2.48
+                p.spec = B <= 11 ? spec_timing(0, "DS2_GRU_FWD5_SPEC", 3, 1, 5) : spec_timing(0, "DS2_GRU_FWD5_SPEC", 8, 1, 6);
+                return p;
+            }
+        }
+        // the k-balanced deal: built for H = 800 (KPL = 25), the BASELINE configs' width, in the forms without a B set
+        // (measured, us per forward step, hand-off timing (10, 1, 2) -> (8, 1, 5): B = 8 2.15 -> 2.05, B = 6 1.97 -> 1.94,
+        // B = 5 1.99 -> 1.94)
+        if (p.proto != 0 && p.tiles == 1 && (3 * p.units / 4) % 4 != 2 && kbal_kpl(H, bper, p.proto) == 25) {
+            p.form = FORM_KBAL;
+            p.spec = spec_timing(0, "DS2_GRU_FWD4_SPEC", 8, 1, 5);
+        }
+        return p;
+    }
+    // (round 4, us per step at H = 800: the split-operand two-part form costs 3.32-3.36 whatever B <= 32 is; the whole-batch
+    // 16x16x4 form 3.63 at B = 16 -- so the split form takes over as soon as the 4x4x1 forms end, at B = 13)
+    const char* p2e = ds2_tune_env("DS2_GRU_FWD_P2");
+    const bool p2 = (p2e ? p2e[0] == '1' : B >= (p2_bf16(H) ? 13 : 17)) && B >= 2 && H % 16 == 0;
+    return plan16(B, p2, p2_bf16(H));
+}
+
+// Units per workgroup of the three-part speculative backward forms (B = 9 .. 12) by the compute units the caller wants left
+// free (see ds2_gru_bidir_bwd_persistent_ex); DS2_GRU_BWD_WIDE = 0 / 1 / 2 forces 24 / 28 / 20 (A/B timing).  The d(h) forms
+// at the test width (H = 64, where every grid is small) go by the request alone.
+inline int bwd_units(int H, int spare_cus, bool dh, int cus, int max_wgs) {
+    int want = spare_cus < 0 ? 52 : spare_cus;
+    const char* w = ds2_tune_env("DS2_GRU_BWD_WIDE");
+    if (w && w[0] >= '0' && w[0] <= '2') want = w[0] == '0' ? 52 : (w[0] == '1' ? 82 : 0);
+    if (dh && H != 800) return want >= 80 ? 28 : (want >= 40 ? 24 : 20);
+    const int g20 = 6 * ds2_cdiv(H, 20), g24 = 6 * ds2_cdiv(H, 24), g28 = 6 * ds2_cdiv(H, 28);
+    if (g20 <= max_wgs && g20 > g24 && cus - g20 >= want) return 20;   // 240 workgroups at H = 800
+    if (cus - g24 >= want || g28 >= g24) return 24;                     // 204
+    return 28;                                                           // 174
+}
+
+// Backward form; dh: the d(h) hand-off (ds2_gru_bidir_bwd_persistent_dh: dh_form_ok shapes).  Otherwise the 4x4x1 forms up
+// to B = 16; from B = 17 the two-part 16x16x4 form (us per step at H = 800, B = 32 / 64: 4x4x1 7.0 / 12.3, see
+// gru_bwd_persistent_p2_kernel).  DS2_GRU_BWD = "4" / "16" forces a family, DS2_GRU_BWD_P2 = 0 / 1 the two-part 16x16x4 form
+// off / on (A/B timing).
+inline GruPlan bwd_plan(int B, int H, int spare_cus, bool dh, int cus, int max_wgs) {
+    if (dh) {                                   // three parts of one batch quad (B = 9 .. 12) or two of 16 units (B = 5 .. 8)
+        const int units = B >= 9 ? bwd_units(H, spare_cus, true, cus, max_wgs) : 16;
+        return {FORM_DH, B >= 9 ? 3 : 2, 1, 2, units, spec_timing(1, "DS2_GRU_BWD6_SPEC", 8, 1, 5)};
+    }
+    const char* form = getenv("DS2_GRU_BWD");
+    const char* p2e = ds2_tune_env("DS2_GRU_BWD_P2");
+    const bool p2 = (p2e ? p2e[0] == '1' : (B >= 17 && !(form && form[0] == '4'))) && B >= 2 && H % 16 == 0;
+    // (round 5, measured and removed: 17 <= B <= 32 on the 4x4x1 instruction with 32 units and a QUARTER of the batch per
+    // workgroup -- half the hand-off bytes of the two-part form per multiply-add, counted hand-off -- B = 32 / 24 / 17: 5.00 /
+    // 4.70 / 4.52 us per step against 4.74 / 4.58 / 4.48: the 4x4x1 instruction retires a multiply-add in 10 cycles / 256 where
+    // the 16x16x4 one takes 32 / 1024, and the bytes are not what bounds the two-part form: from B = 17 to 32 its part grows
+    // from 9 to 16 rows, 84 to 150 KB per workgroup and step, and the step by 0.26 us -- profiles/r05_recurrence_experiments.md)
+    if (p2) {
+        // (the backward twin is hand-off-bound, not matrix-bound -- three gates' values cross per step, and as bf16 planes
+        // they are 1.5 x the bytes: 4.91 against 4.74 us per step at B = 32, 8.46 against 7.57 at B = 64; DS2_GRU_P2_BF16_BWD=1
+        // selects it for A/B runs)
+        const char* bf16 = getenv("DS2_GRU_P2_BF16_BWD");
+        return plan16(B, true, p2_bf16(H) && bf16 && bf16[0] == '1');
+    }
+    if ((form && form[0] != '4') || ds2_cdiv(ds2_cdiv(3 * H, 64), NWP) > 5) return plan16(B, false, false);   // (no 4x4x1 form)
+    // Batch parts (1, 2 or 3: 8, 16 or 24 units per workgroup) by the fitted cost model; measured, H = 800, us per step,
+    // whole batch / two halves: B=8 3.32 / 2.98, B=10 3.90 / 4.04, B=16 4.77 / 4.09, B=32 7.48 / 6.51, B=64 12.84 / 11.38.
+    // DS2_GRU_BWD_SPLIT = 1 / 2 / 3 forces a form (A/B timing).
+    int parts = 1;
+    double best = 1e30;
+    for (int p = 1; p <= 3; ++p) {
+        if (p > B || 2 * ds2_cdiv(H, 8 * p) * p > max_wgs || ds2_cdiv(B, p) * 8 * p > NWP * 64) continue;
+        const int bper = ds2_cdiv(B, p), quads = (bper + 3) / 4;
+        const double cost = 0.40 * quads * p + 0.34 * bper / 4.0 + (p == 3 && quads > 2 ? 0.3 : 0.0);
+        if (cost < best - 1e-9) {
+            best = cost;
+            parts = p;
+        }
+    }
+    const char* split = ds2_tune_env("DS2_GRU_BWD_SPLIT");
+    if (split && split[0] >= '1' && split[0] <= '3' && (split[0] - '0') <= B) parts = split[0] - '0';
+    const int proto = handoff_protocol(ds2_cdiv(B, parts));
+    if (proto != 0 && ds2_cdiv(B, parts) <= 4 && parts >= 2) {   // (<= 4: also under a forced DS2_GRU_PROTO)
+        // the broadcast deal: H is a multiple of 16 and a part is one batch quad here.  Three parts, measured stand-alone at
+        // B = 10, us per step, against the 16-k-blocks deal it replaces (gru_bwd_persistent4_kernel<5, NRG, 2, 3>, removed in
+        // round 5), each with its own hand-off timing: 28 units 3.02-3.05 -> 2.86, 24 units 2.79-2.81 -> 2.65, 20 units
+        // 2.61-2.64 -> 2.51-2.54.  Two parts (B = 5 .. 8: 16 units and half the batch per workgroup, set A only: no fold at
+        // all), against gru_bwd_persistent4_kernel<5, 4, 2>, B = 8 / 6 / 5: 2.34 / 2.30 / 2.30 -> 2.20 / 2.15 / 2.11 -- with
+        // round 2's hand-off timing the two were level (2.33-2.37 against 2.34-2.35 at B = 8)
+        const int units = parts == 3 ? bwd_units(H, spare_cus, false, cus, max_wgs) : 16;
+        // (the kernel's hand-off timing, measured at B = 10, us per step, (14, 1, 2) -> (10, 1, 4): 28 units 2.95 -> 2.86, 24
+        // units 2.74 -> 2.65; 20 units 2.67-2.69 -> 2.54, and 2.51 with (10, 1, 5) -- with that the broadcast deal beats the
+        // 16-k-blocks deal's 2.61-2.64 there too)
+        return {FORM_BCAST, parts, 1, proto, units,
+                spec_timing(1, "DS2_GRU_BWD5_SPEC", units == 16 ? 8 : 10, 1, units <= 20 ? 5 : 4)};
+    }
+    // (three parts of more than one quad: the counted protocol)
+    return {FORM_4X4, parts, 1, parts == 3 ? 0 : proto, 8 * parts, spec_timing(1)};
+}
+
+inline bool fwd_launch(const GruPlan& p, float* G, float* ghn, float* hout, const float* w_hh, float* coef, SyncWs* sync,
+                       float* ring, int T, int B, int H, int dbg, hipStream_t st) {
+    if (p.form >= FORM_16) return ds2_p16_launch_fwd(p.form - FORM_16, p.tiles, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st);
+    using std::integral_constant;
+    const dim3 grid(ds2_cdiv(H, p.units), 2, p.parts);
+    const size_t lds = (size_t)((ds2_cdiv(B, p.parts) + 3) / 4) * 4 * 3 * p.units * FWD4_PITCH * sizeof(float);
+    auto go = [&](auto kernel) { return launch_persistent(kernel, grid, lds, st, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, p.spec); };
+    auto k_groups = [&](auto P, auto NBT, auto PROTO, auto UGX) {
+        return with_kbw<1, 2, 3>(ds2_cdiv(ds2_cdiv(H, 64), NWP),
+                                 [&](auto K) { return go(&gru_fwd_persistent4_kernel<K, P, NBT, PROTO, UGX>); });
+    };
+    auto by_proto = [&](auto P, auto NBT) {
+        return p.proto ? k_groups(P, NBT, integral_constant<int, 2>(), integral_constant<int, 0>())
+                       : k_groups(P, NBT, integral_constant<int, 0>(), integral_constant<int, 0>());
+    };
+    switch (p.form) {
+    case FORM_4X4:
+        if (p.units == 20)
+            return k_groups(integral_constant<int, 3>(), integral_constant<int, 1>(), integral_constant<int, 2>(), integral_constant<int, 5>());
+        return with_kbw<1, 2, 3>(p.parts, [&](auto P) { return with_kbw<1, 2>(p.tiles, [&](auto NBT) { return by_proto(P, NBT); }); });
+    case FORM_KBAL:
+        return p.units == 20 ? go(&gru_fwd_persistent4_kernel<1, 3, 1, 2, 5, 25>) : go(&gru_fwd_persistent4_kernel<1, 2, 1, 2, 0, 25>);
+    case FORM_ROWS:
+        return launch_persistent(&gru_fwd_persistent5_kernel<100, 20, 3>, grid, 0, st, G, ghn, hout, w_hh, coef, sync, ring, T, B, H,
+                                 dbg, p.spec);
+    }
+    return false;
+}
+
+inline bool bwd_launch(const GruPlan& p, float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
+                       const float* coef, SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
+    if (p.form >= FORM_16)
+        return ds2_p16_launch_bwd(p.form - FORM_16, p.tiles, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
+    using std::integral_constant;
+    const dim3 grid(ds2_cdiv(H, p.units), 2, p.parts);
+    auto go = [&](auto kernel, size_t lds) {
+        return launch_persistent(kernel, grid, lds, st, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, p.spec);
+    };
+    const int kbw = ds2_cdiv(ds2_cdiv(3 * H, 64), NWP);
+    auto k_groups = [&](auto NRG, auto PROTO) {
+        const size_t lds = (size_t)NRG * ((ds2_cdiv(B, p.parts) + 3) / 4) * 16 * RED4_PITCH * sizeof(float);
+        return with_kbw<1, 2, 3, 5>(kbw, [&](auto K) { return go(&gru_bwd_persistent4_kernel<K, NRG, PROTO>, lds); });
+    };
+    auto bcast = [&](auto NRG, auto NPART) {
+        return with_kbw<1, 2, 3, 5>(kbw, [&](auto K) { return go(&gru_bwd_persistent5_kernel<K, NRG, NPART>, 0); });
+    };
+    auto dh = [&](auto RPW, auto NRG, auto NPART) {
+        auto kernel = &gru_bwd_persistent6_kernel<RPW, NRG, NPART>;
+#if defined(DS2_TIMING) || defined(DS2_FAULT_INJECT)
+        // the ablated instantiations bench.py's floor leg and the timing tools ask for (the forms of a B = 9 .. 12 step at H = 800)
+        if constexpr (RPW == 25 && NPART == 3 && (NRG == 5 || NRG == 7)) {
+            const int abl = dbg & (2 | 2048 | 4096 | 8192);
+            if (abl == (2 | 8192) || abl == 2) kernel = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 2 | 8192>;
+            else if (abl == (2048 | 8192) || abl == 2048) kernel = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 2048 | 8192>;
+            else if (abl == (4096 | 8192) || abl == 4096) kernel = &gru_bwd_persistent6_kernel<RPW, NRG, NPART, 4096 | 8192>;
+        }
+#endif
+        return launch_persistent(kernel, grid, 0, st, G, ghn, hout, d_out, w_hh_t, coef, sync, ring, T, B, H, dbg, p.spec);
+    };
+    auto dh_width = [&](auto RPW) {            // H = 32 RPW
+        if (p.parts == 2) return dh(RPW, integral_constant<int, 4>(), integral_constant<int, 2>());
+        return with_kbw<5, 6, 7>(p.units / 4, [&](auto NRG) { return dh(RPW, NRG, integral_constant<int, 3>()); });
+    };
+    switch (p.form) {
+    case FORM_4X4:
+        if (p.parts == 3) return k_groups(integral_constant<int, 6>(), integral_constant<int, 0>());
+        if (p.parts == 2)
+            return p.proto ? k_groups(integral_constant<int, 4>(), integral_constant<int, 2>())
+                           : k_groups(integral_constant<int, 4>(), integral_constant<int, 0>());
+        return p.proto ? k_groups(integral_constant<int, 2>(), integral_constant<int, 2>())
+                       : k_groups(integral_constant<int, 2>(), integral_constant<int, 0>());
+    case FORM_BCAST:
+        if (p.parts == 2) return bcast(integral_constant<int, 4>(), integral_constant<int, 2>());
+        return with_kbw<5, 6, 7>(p.units / 4, [&](auto NRG) { return bcast(NRG, integral_constant<int, 3>()); });
+    case FORM_DH:
+        return H == 800 ? dh_width(integral_constant<int, 25>()) : dh_width(integral_constant<int, 2>());
+    }
+    return false;
+}
+
+}  // namespace
+
+// A data-tagged-granule hand-off (Guideline 16 R2: every consumer wave polls the 8-byte {value, epoch} granules it
+// needs) was built and measured in round 1: correct, but 1.5x (forward) to 2.1x (backward) SLOWER per step than the
+// counter form -- 1600 waves polling payload lines swamp the fabric ("polling-cost" row of the price list).
+// exchange ring: [dir 2][slot 2][batch tiles][k blocks of 16][16][16] floats, sized for the backward pass (K = 3H)
 inline size_t ring_floats(int B, int H) {
     const int tiles16 = ds2_cdiv(B, 16) > 2 * ds2_cdiv(ds2_cdiv(B, 2), 16) ? ds2_cdiv(B, 16) : 2 * ds2_cdiv(ds2_cdiv(B, 2), 16);
     const size_t a = (size_t)tiles16 * (size_t)(3 * H / 16) * 256 * 3 / 2 + 4096;     // 16x16 forms (whole batch / two parts;
@@ -2248,77 +2339,17 @@ extern "C" int ds2_gru_bidir_fwd_persistent_ex(float* G, float* ghn, float* hout
         ds2_set_error("ds2_gru_bidir_fwd_persistent: unsupported shape B=%d H=%d", B, H);
         return DS2_ERR_UNSUPPORTED;
     }
-    hipStream_t st = (hipStream_t)stream;
-    SyncWs* sync = (SyncWs*)sync_ws;
     float* ring = (float*)((char*)sync_ws + header_bytes());
     // No memset: the previous launch left the counters zero (leave_kernel) and nothing reads ring bytes that this
     // launch has not written, except the padding batch columns of the 16x16x4 forms, whose products land in output
     // columns no gate thread reads.
-    const int dbg = dbg_flags();
-    bool ok;
-    // Form by batch size.  Measured (H = 800, us per step, 4x4x1 broadcast form with the whole batch per workgroup vs
-    // 16x16x4 form): B=4 2.57 / 3.65, B=10 3.84 / 3.88, B=16 4.41 / 3.89, B=32 7.44 / 5.56 -- the 4x4x1 form's cost
-    // grows with every batch quad (and, with batch parts, with quads x parts for the MFMAs but only quads for the
-    // loads), the 16x16x4 form's with every tile of 16.  DS2_GRU_FWD = "4" / "16" forces a form, DS2_GRU_FWD_SPLIT =
-    // 1 / 2 / 3 the number of batch parts (A/B timing).
-    const char* form = getenv("DS2_GRU_FWD");
-    const bool ngi_ok = ds2_cdiv(ds2_cdiv(H, 64), NWP) <= 3;
-    int parts = B <= 4 ? 1 : (B <= 8 ? 2 : 3);
-    {
-        const char* split = ds2_tune_env("DS2_GRU_FWD_SPLIT");
-        if (split && split[0] >= '1' && split[0] <= '3') parts = split[0] - '0';
-        if (parts > B) parts = B;
-        // gate-role capacity: two passes of 512 / (4 * 8 parts) batch rows per workgroup; all workgroups co-resident
-        while (parts < 3 && ds2_cdiv(B, parts) > 2 * (NWP * 64 / (32 * parts))) ++parts;
-        if (2 * ds2_cdiv(H, 8 * parts) * parts > max_persistent_wgs()) parts = 1;
-    }
-    const int bper = ds2_cdiv(B, parts), rpp = NWP * 64 / (32 * parts);
-    const bool fits4 = ngi_ok && bper <= 2 * rpp && (size_t)((bper + 3) / 4) * 4 * 24 * parts * FWD4_PITCH * 4 <= 140 * 1024;
-    const bool use4 = (form ? form[0] == '4' : B <= 12) && fits4;
-    if (use4) {
-        const bool two = bper > rpp;
-#define DS2_FWD4_GO(P_, N_)                                                                                         \
-    (proto != 0 ? launch_fwd_persistent4<P_, N_, 2>(G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st)                \
-                : launch_fwd_persistent4<P_, N_, 0>(G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st))
-        const int proto = handoff_protocol(bper);
-        // three parts, one batch quad each, speculative hand-off (B = 9 .. 12): 20-unit slices on 240 CUs when they fit
-        const char* wide = getenv("DS2_GRU_FWD_WIDE");
-        if (parts == 3 && !two && proto != 0 && (wide ? wide[0] == '1' : true) && H % 4 == 0 &&
-            6 * ds2_cdiv(H, 20) <= max_persistent_wgs() && 6 * ds2_cdiv(H, 20) > 6 * ds2_cdiv(H, 24)) {
-            // the row deal where it is built (H = 800: 100 columns per wave); DS2_GRU_FWD_ROWS = 0: the k-balanced deal (A/B timing)
-            const char* rows = ds2_tune_env("DS2_GRU_FWD_ROWS");
-            if (H == 800 && bper <= 4 && !(rows && rows[0] == '0'))
-            {
-                ok = launch_fwd_persistent5<100>(G, ghn, hout, w_hh, coef, sync, ring, T, B, H, dbg, st);
-                if (ok) coef = nullptr;                   // written by the kernel itself
-            }
-            else
-                ok = launch_fwd_persistent4<3, 1, 2, 5>(G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st);
-        }
-        // (the row deal with two batch parts -- 20 units, 160 workgroups -- measured at B = 8: 2.30 us per step against 2.15 for
-        // the 16-unit k-balanced form on 200: its 48 gate rows fill 12 of the 16 blocks, the row deal would issue 100 MFMAs for 75)
-        else
-        if (parts == 1) ok = two ? DS2_FWD4_GO(1, 2) : DS2_FWD4_GO(1, 1);
-        else if (parts == 2) ok = two ? DS2_FWD4_GO(2, 2) : DS2_FWD4_GO(2, 1);
-        else ok = two ? DS2_FWD4_GO(3, 2) : DS2_FWD4_GO(3, 1);
-#undef DS2_FWD4_GO
-    }
-    // (round 4, us per step at H = 800: the split-operand two-part form costs 3.32-3.36 whatever B <= 32 is; the whole-batch
-    // 16x16x4 form 3.63 at B = 16 -- so the split form takes over as soon as the 4x4x1 forms end, at B = 13)
-    else if ((ds2_tune_env("DS2_GRU_FWD_P2") ? ds2_tune_env("DS2_GRU_FWD_P2")[0] == '1' : B >= (p2_bf16(H) ? 13 : 17)) && B >= 2 && H % 16 == 0)
-        ok = p2_bf16(H) ? ((B + 1) / 2 <= 16 ? ds2_p16_launch_fwd(2, 1, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st)
-                                             : ds2_p16_launch_fwd(2, 2, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st))
-                        : ((B + 1) / 2 <= 16 ? ds2_p16_launch_fwd(1, 1, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st)
-                                             : ds2_p16_launch_fwd(1, 2, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st));
-    else if (B <= 16) ok = ds2_p16_launch_fwd(0, 1, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st);
-    else if (B <= 32) ok = ds2_p16_launch_fwd(0, 2, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st);
-    else ok = ds2_p16_launch_fwd(0, 4, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st);
-    if (!ok) {
+    const GruPlan plan = fwd_plan(B, H, max_persistent_wgs());
+    if (!fwd_launch(plan, G, ghn, hout, w_hh, coef, (SyncWs*)sync_ws, ring, T, B, H, dbg_flags(), (hipStream_t)stream)) {
         ds2_set_error("ds2_gru_bidir_fwd_persistent: the chosen kernel's grid is not co-resident on this device (B=%d H=%d)", B, H);
         return DS2_ERR_UNSUPPORTED;
     }
     DS2_CHECK_LAUNCH();
-    if (coef) return ds2_gru_bwd_coef(G, ghn, hout, coef, T, B, H, stream);
+    if (coef && plan.form != FORM_ROWS) return ds2_gru_bwd_coef(G, ghn, hout, coef, T, B, H, stream);
     return DS2_OK;
 }
 
@@ -2348,86 +2379,9 @@ extern "C" int ds2_gru_bidir_bwd_persistent_ex(float* G, float* ghn, const float
         ds2_set_error("ds2_gru_bidir_bwd_persistent: unsupported shape B=%d H=%d", B, H);
         return DS2_ERR_UNSUPPORTED;
     }
-    hipStream_t st = (hipStream_t)stream;
-    SyncWs* sync = (SyncWs*)sync_ws;
     float* ring = (float*)((char*)sync_ws + header_bytes());
-    const int dbg = dbg_flags();
-    bool ok;
-    // Form: the 4x4x1 forms up to B = 16; from B = 17 the two-part 16x16x4 form (us per step at H = 800, B = 32 / 64: 4x4x1
-    // 7.0 / 12.3, see gru_bwd_persistent_p2_kernel).  DS2_GRU_BWD = "4" / "16" forces a family, DS2_GRU_BWD_P2 = 0 / 1 the
-    // two-part 16x16x4 form off / on (A/B timing).
-    const char* form = getenv("DS2_GRU_BWD");
-    const char* p2e = ds2_tune_env("DS2_GRU_BWD_P2");
-    const bool p2 = (p2e ? p2e[0] == '1' : (B >= 17 && !(form && form[0] == '4'))) && B >= 2 && H % 16 == 0;
-    const bool use4 = !p2 && (form ? form[0] == '4' : true);
-    // Batch parts (1, 2 or 3: 8, 16 or 24 units per workgroup) by the fitted cost model; measured, H = 800, us per step,
-    // whole batch / two halves: B=8 3.32 / 2.98, B=10 3.90 / 4.04, B=16 4.77 / 4.09, B=32 7.48 / 6.51, B=64 12.84 / 11.38.
-    // DS2_GRU_BWD_SPLIT = 1 / 2 / 3 forces a form (A/B timing).
-    int parts = 1;
-    {
-        double best = 1e30;
-        for (int p = 1; p <= 3; ++p) {
-            if (p > B || 2 * ds2_cdiv(H, 8 * p) * p > max_persistent_wgs() || ds2_cdiv(B, p) * 8 * p > NWP * 64) continue;
-            const int bper = ds2_cdiv(B, p), quads = (bper + 3) / 4;
-            const double cost = 0.40 * quads * p + 0.34 * bper / 4.0 + (p == 3 && quads > 2 ? 0.3 : 0.0);
-            if (cost < best - 1e-9) {
-                best = cost;
-                parts = p;
-            }
-        }
-        const char* split = ds2_tune_env("DS2_GRU_BWD_SPLIT");
-        if (split && split[0] >= '1' && split[0] <= '3' && (split[0] - '0') <= B) parts = split[0] - '0';
-    }
-    const bool ngi_ok = ds2_cdiv(ds2_cdiv(3 * H, 64), NWP) <= 5;
-    const int proto = handoff_protocol(ds2_cdiv(B, parts));
-#define DS2_BWD4_GO(R_)                                                                                             \
-    (proto != 0 ? launch_bwd_persistent4<R_, 2>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st)           \
-                : launch_bwd_persistent4<R_, 0>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st))
-    // (round 5, measured and removed: 17 <= B <= 32 on the 4x4x1 instruction with 32 units and a QUARTER of the batch per
-    // workgroup -- half the hand-off bytes of the two-part form per multiply-add, counted hand-off -- B = 32 / 24 / 17: 5.00 /
-    // 4.70 / 4.52 us per step against 4.74 / 4.58 / 4.48: the 4x4x1 instruction retires a multiply-add in 10 cycles / 256 where
-    // the 16x16x4 one takes 32 / 1024, and the bytes are not what bounds the two-part form: from B = 17 to 32 its part grows
-    // from 9 to 16 rows, 84 to 150 KB per workgroup and step, and the step by 0.26 us -- profiles/r05_recurrence_experiments.md)
-    if (p2)
-        // (the backward twin is hand-off-bound, not matrix-bound -- three gates' values cross per step, and as bf16 planes
-        // they are 1.5 x the bytes: 4.91 against 4.74 us per step at B = 32, 8.46 against 7.57 at B = 64; DS2_GRU_P2_BF16_BWD=1
-        // selects it for A/B runs)
-        ok = (p2_bf16(H) && getenv("DS2_GRU_P2_BF16_BWD") && getenv("DS2_GRU_P2_BF16_BWD")[0] == '1')
-                 ? ((B + 1) / 2 <= 16 ? ds2_p16_launch_bwd(2, 1, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st)
-                                      : ds2_p16_launch_bwd(2, 2, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st))
-                 : ((B + 1) / 2 <= 16 ? ds2_p16_launch_bwd(1, 1, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st)
-                                      : ds2_p16_launch_bwd(1, 2, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st));
-    else if (use4 && ngi_ok && parts == 3 && proto != 0 && ds2_cdiv(B, 3) <= 4) {   // (<= 4: also under a forced DS2_GRU_PROTO)
-        // units per workgroup by the CUs to leave free (see above); DS2_GRU_BWD_WIDE = 0 / 1 / 2 forces 24 / 28 / 20 (A/B timing)
-        const int cus = device_cus();
-        int want = spare_cus < 0 ? 52 : spare_cus;
-        const char* w = ds2_tune_env("DS2_GRU_BWD_WIDE");
-        if (w && w[0] >= '0' && w[0] <= '2') want = w[0] == '0' ? 52 : (w[0] == '1' ? 82 : 0);
-        const int g20 = 6 * ds2_cdiv(H, 20), g24 = 6 * ds2_cdiv(H, 24), g28 = 6 * ds2_cdiv(H, 28);
-        // the broadcast deal (gru_bwd_persistent5_kernel): H is a multiple of 16 and a part is one batch quad here.  Measured
-        // stand-alone at B = 10, us per step, against the 16-k-blocks deal it replaces (gru_bwd_persistent4_kernel<5, NRG, 2, 3>,
-        // removed in round 5), each with its own hand-off timing: 28 units 3.02-3.05 -> 2.86, 24 units 2.79-2.81 -> 2.65,
-        // 20 units 2.61-2.64 -> 2.51-2.54
-        if (g20 <= max_persistent_wgs() && g20 > g24 && cus - g20 >= want)
-            ok = launch_bwd_persistent5<5>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);         // 240 workgroups
-        else if (cus - g24 >= want || g28 >= g24)
-            ok = launch_bwd_persistent5<6>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);         // 204
-        else
-            ok = launch_bwd_persistent5<7>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);         // 174
-    }
-    else if (use4 && ngi_ok && parts == 3)           // (three parts of more than one quad: the counted protocol)
-        ok = launch_bwd_persistent4<6, 0>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
-    else if (use4 && ngi_ok && parts == 2 && proto != 0 && ds2_cdiv(B, 2) <= 4)
-        // B = 5 .. 8: 16 units and half the batch per workgroup in the broadcast deal (set A only: no fold at all).  us per
-        // step against the 16-k-blocks deal (gru_bwd_persistent4_kernel<5, 4, 2>), B = 8 / 6 / 5: 2.34 / 2.30 / 2.30 -> 2.20 /
-        // 2.15 / 2.11 -- with round 2's hand-off timing the two were level (2.33-2.37 against 2.34-2.35 at B = 8)
-        ok = launch_bwd_persistent5<4, 2>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
-    else if (use4 && ngi_ok && parts == 2) ok = DS2_BWD4_GO(4);
-    else if (use4 && ngi_ok) ok = DS2_BWD4_GO(2);
-    else if (B <= 16) ok = ds2_p16_launch_bwd(0, 1, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
-    else if (B <= 32) ok = ds2_p16_launch_bwd(0, 2, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
-    else ok = ds2_p16_launch_bwd(0, 4, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st);
-    if (!ok) {
+    const GruPlan plan = bwd_plan(B, H, spare_cus, false, device_cus(), max_persistent_wgs());
+    if (!bwd_launch(plan, G, ghn, hout, d_out, w_hh_t, nullptr, (SyncWs*)sync_ws, ring, T, B, H, dbg_flags(), (hipStream_t)stream)) {
         ds2_set_error("ds2_gru_bidir_bwd_persistent: the chosen kernel's grid is not co-resident on this device (B=%d H=%d)", B, H);
         return DS2_ERR_UNSUPPORTED;
     }
@@ -2462,30 +2416,9 @@ extern "C" int ds2_gru_bidir_bwd_persistent_dh(float* G, float* ghn, const float
         ds2_set_error("ds2_gru_bidir_bwd_persistent_dh: unsupported shape B=%d H=%d", B, H);
         return DS2_ERR_UNSUPPORTED;
     }
-    hipStream_t st = (hipStream_t)stream;
-    SyncWs* sync = (SyncWs*)sync_ws;
     float* ring = (float*)((char*)sync_ws + header_bytes());
-    const int dbg = dbg_flags();
-    bool ok = false;
-#define DS2_BWD6_GO(RPW_, NRG_, NP_) launch_bwd_persistent6<RPW_, NRG_, NP_>(G, ghn, hout, d_out, w_hh_t, coef, sync, ring, T, B, H, dbg, st)
-    if (B >= 9) {                                       // three parts of one batch quad: units per workgroup by the CUs to leave free
-        const int cus = device_cus();
-        int want = spare_cus < 0 ? 52 : spare_cus;
-        const char* w = ds2_tune_env("DS2_GRU_BWD_WIDE");
-        if (w && w[0] >= '0' && w[0] <= '2') want = w[0] == '0' ? 52 : (w[0] == '1' ? 82 : 0);
-        const int g20 = 6 * ds2_cdiv(H, 20), g24 = 6 * ds2_cdiv(H, 24), g28 = 6 * ds2_cdiv(H, 28);
-        if (H == 800) {
-            if (g20 <= max_persistent_wgs() && g20 > g24 && cus - g20 >= want) ok = DS2_BWD6_GO(25, 5, 3);
-            else if (cus - g24 >= want || g28 >= g24) ok = DS2_BWD6_GO(25, 6, 3);
-            else ok = DS2_BWD6_GO(25, 7, 3);
-        } else {
-            ok = want >= 80 ? DS2_BWD6_GO(2, 7, 3) : (want >= 40 ? DS2_BWD6_GO(2, 6, 3) : DS2_BWD6_GO(2, 5, 3));
-        }
-    } else {                                            // B = 5 .. 8: two parts, 16 units
-        ok = H == 800 ? DS2_BWD6_GO(25, 4, 2) : DS2_BWD6_GO(2, 4, 2);
-    }
-#undef DS2_BWD6_GO
-    if (!ok) {
+    const GruPlan plan = bwd_plan(B, H, spare_cus, true, device_cus(), max_persistent_wgs());
+    if (!bwd_launch(plan, G, ghn, hout, d_out, w_hh_t, coef, (SyncWs*)sync_ws, ring, T, B, H, dbg_flags(), (hipStream_t)stream)) {
         ds2_set_error("ds2_gru_bidir_bwd_persistent_dh: the chosen kernel's grid is not co-resident on this device (B=%d H=%d)", B, H);
         return DS2_ERR_UNSUPPORTED;
     }

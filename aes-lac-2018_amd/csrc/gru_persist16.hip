@@ -1010,157 +1010,44 @@ __global__ __launch_bounds__(NWP * 64) void gru_bwd_persistent_p2b_kernel(float*
 }
 
 
-template <int NBT>
-bool launch_fwd_persistent(float* G, float* ghn, float* hout, const float* w_hh, SyncWs* sync, float* ring, int T, int B,
-                           int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 4, 7};
-    const int kbw = pick_kbw(ds2_cdiv(H / 16, NWP), opts, 4);
-    dim3 grid(ds2_cdiv(H, PJU), 2), block(NWP * 64);
-#define DS2_FWD_CASE(K)                                                                                              \
-    case K:                                                                                                          \
-        if (!grid_is_coresident(&gru_fwd_persistent_kernel<NBT, K>, grid, 0)) return false;                          \
-        hipLaunchKernelGGL((gru_fwd_persistent_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, w_hh, sync, ring, T, B,  \
-                           H, dbg);                                                                                   \
-        return true;
-    switch (kbw) {
-        DS2_FWD_CASE(1)
-        DS2_FWD_CASE(2)
-        DS2_FWD_CASE(4)
-        DS2_FWD_CASE(7)
-    }
-#undef DS2_FWD_CASE
-    return false;
-}
-
-template <int NBT>
-bool launch_fwd_persistent_p2(float* G, float* ghn, float* hout, const float* w_hh, SyncWs* sync, float* ring, int T, int B,
-                              int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 4, 7};
-    const int kbw = pick_kbw(ds2_cdiv(H / 16, NWP), opts, 4);
-    dim3 grid(ds2_cdiv(H, 16), 2, 2), block(NWP * 64);
-#define DS2_FWDP2_CASE(K)                                                                                          \
-    case K:                                                                                                        \
-        if (!grid_is_coresident(&gru_fwd_persistent_p2_kernel<NBT, K>, grid, 0)) return false;                     \
-        hipLaunchKernelGGL((gru_fwd_persistent_p2_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, w_hh, sync, ring,   \
-                           T, B, H, dbg);                                                                          \
-        return true;
-    switch (kbw) {
-        DS2_FWDP2_CASE(1)
-        DS2_FWDP2_CASE(2)
-        DS2_FWDP2_CASE(4)
-        DS2_FWDP2_CASE(7)
-    }
-#undef DS2_FWDP2_CASE
-    return false;
-}
-
-template <int NBT>
-bool launch_fwd_persistent_p2b(float* G, float* ghn, float* hout, const float* w_hh, SyncWs* sync, float* ring, int T, int B,
-                               int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 4};
-    const int kbw = pick_kbw(ds2_cdiv(H / 32, NWP), opts, 3);
-    dim3 grid(ds2_cdiv(H, 16), 2, 2), block(NWP * 64);
-#define DS2_FWDP2B_CASE(K)                                                                                         \
-    case K:                                                                                                        \
-        if (!grid_is_coresident(&gru_fwd_persistent_p2b_kernel<NBT, K>, grid, 0)) return false;                    \
-        hipLaunchKernelGGL((gru_fwd_persistent_p2b_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, w_hh, sync, ring,  \
-                           T, B, H, dbg);                                                                          \
-        return true;
-    switch (kbw) {
-        DS2_FWDP2B_CASE(1)
-        DS2_FWDP2B_CASE(2)
-        DS2_FWDP2B_CASE(4)
-    }
-#undef DS2_FWDP2B_CASE
-    return false;
-}
-
-template <int NBT>
-bool launch_bwd_persistent(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
-                           SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 4, 8, 19};
-    const int kbw = pick_kbw(ds2_cdiv(3 * H / 16, NWP), opts, 5);
-    dim3 grid(ds2_cdiv(H, PJU), 2), block(NWP * 64);
-#define DS2_BWD_CASE(K)                                                                                          \
-    case K:                                                                                                      \
-        if (!grid_is_coresident(&gru_bwd_persistent_kernel<NBT, K>, grid, 0)) return false;                      \
-        hipLaunchKernelGGL((gru_bwd_persistent_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, d_out, w_hh_t, \
-                           sync, ring, T, B, H, dbg);                                                            \
-        return true;
-    switch (kbw) {
-        DS2_BWD_CASE(1)
-        DS2_BWD_CASE(2)
-        DS2_BWD_CASE(4)
-        DS2_BWD_CASE(8)
-        DS2_BWD_CASE(19)
-    }
-#undef DS2_BWD_CASE
-    return false;
-}
-
-template <int NBT>
-bool launch_bwd_persistent_p2(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
-                              SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 4, 8, 19};
-    const int kbw = pick_kbw(ds2_cdiv(3 * H / 16, NWP), opts, 5);
-    dim3 grid(ds2_cdiv(H, 16), 2, 2), block(NWP * 64);
-#define DS2_BWDP2_CASE(K)                                                                                          \
-    case K:                                                                                                        \
-        if (!grid_is_coresident(&gru_bwd_persistent_p2_kernel<NBT, K>, grid, 0)) return false;                     \
-        hipLaunchKernelGGL((gru_bwd_persistent_p2_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, d_out, w_hh_t, \
-                           sync, ring, T, B, H, dbg);                                                              \
-        return true;
-    switch (kbw) {
-        DS2_BWDP2_CASE(1)
-        DS2_BWDP2_CASE(2)
-        DS2_BWDP2_CASE(4)
-        DS2_BWDP2_CASE(8)
-        DS2_BWDP2_CASE(19)
-    }
-#undef DS2_BWDP2_CASE
-    return false;
-}
-
-template <int NBT>
-bool launch_bwd_persistent_p2b(float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
-                               SyncWs* sync, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
-    const int opts[] = {1, 2, 5, 10};
-    const int kbw = pick_kbw(ds2_cdiv(3 * H / 32, NWP), opts, 4);
-    dim3 grid(ds2_cdiv(H, 16), 2, 2), block(NWP * 64);
-#define DS2_BWDP2B_CASE(K)                                                                                          \
-    case K:                                                                                                         \
-        if (!grid_is_coresident(&gru_bwd_persistent_p2b_kernel<NBT, K>, grid, 0)) return false;                     \
-        hipLaunchKernelGGL((gru_bwd_persistent_p2b_kernel<NBT, K>), grid, block, 0, st, G, ghn, hout, d_out, w_hh_t, \
-                           sync, ring, T, B, H, dbg);                                                               \
-        return true;
-    switch (kbw) {
-        DS2_BWDP2B_CASE(1)
-        DS2_BWDP2B_CASE(2)
-        DS2_BWDP2B_CASE(5)
-        DS2_BWDP2B_CASE(10)
-    }
-#undef DS2_BWDP2B_CASE
-    return false;
-}
-
 }  // namespace
 
 bool ds2_p16_launch_fwd(int form, int nbt, float* G, float* ghn, float* hout, const float* w_hh, void* sync_, float* ring, int T,
                         int B, int H, int dbg, hipStream_t st) {
     SyncWs* sync = (SyncWs*)sync_;
-#define DS2_P16_F(FN, N) FN<N>(G, ghn, hout, w_hh, sync, ring, T, B, H, dbg, st)
-    if (form == 0) return nbt == 1 ? DS2_P16_F(launch_fwd_persistent, 1) : (nbt == 2 ? DS2_P16_F(launch_fwd_persistent, 2) : DS2_P16_F(launch_fwd_persistent, 4));
-    if (form == 1) return nbt == 1 ? DS2_P16_F(launch_fwd_persistent_p2, 1) : DS2_P16_F(launch_fwd_persistent_p2, 2);
-    return nbt == 1 ? DS2_P16_F(launch_fwd_persistent_p2b, 1) : DS2_P16_F(launch_fwd_persistent_p2b, 2);
-#undef DS2_P16_F
+    const dim3 whole(ds2_cdiv(H, PJU), 2), halves(ds2_cdiv(H, 16), 2, 2);
+    const int kbw = ds2_cdiv(H / 16, NWP), kbw_bf16 = ds2_cdiv(H / 32, NWP);
+    auto go = [&](auto kernel, dim3 grid) { return launch_persistent(kernel, grid, 0, st, G, ghn, hout, w_hh, sync, ring, T, B, H, dbg); };
+    if (form == 0)
+        return with_kbw<1, 2, 4>(nbt, [&](auto N) {
+            return with_kbw<1, 2, 4, 7>(kbw, [&](auto K) { return go(&gru_fwd_persistent_kernel<N, K>, whole); });
+        });
+    if (form == 1)
+        return with_kbw<1, 2>(nbt, [&](auto N) {
+            return with_kbw<1, 2, 4, 7>(kbw, [&](auto K) { return go(&gru_fwd_persistent_p2_kernel<N, K>, halves); });
+        });
+    return with_kbw<1, 2>(nbt, [&](auto N) {
+        return with_kbw<1, 2, 4>(kbw_bf16, [&](auto K) { return go(&gru_fwd_persistent_p2b_kernel<N, K>, halves); });
+    });
 }
 
 bool ds2_p16_launch_bwd(int form, int nbt, float* G, float* ghn, const float* hout, const float* d_out, const float* w_hh_t,
                         void* sync_, float* ring, int T, int B, int H, int dbg, hipStream_t st) {
     SyncWs* sync = (SyncWs*)sync_;
-#define DS2_P16_B(FN, N) FN<N>(G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg, st)
-    if (form == 0) return nbt == 1 ? DS2_P16_B(launch_bwd_persistent, 1) : (nbt == 2 ? DS2_P16_B(launch_bwd_persistent, 2) : DS2_P16_B(launch_bwd_persistent, 4));
-    if (form == 1) return nbt == 1 ? DS2_P16_B(launch_bwd_persistent_p2, 1) : DS2_P16_B(launch_bwd_persistent_p2, 2);
-    return nbt == 1 ? DS2_P16_B(launch_bwd_persistent_p2b, 1) : DS2_P16_B(launch_bwd_persistent_p2b, 2);
-#undef DS2_P16_B
+    const dim3 whole(ds2_cdiv(H, PJU), 2), halves(ds2_cdiv(H, 16), 2, 2);
+    const int kbw = ds2_cdiv(3 * H / 16, NWP), kbw_bf16 = ds2_cdiv(3 * H / 32, NWP);
+    auto go = [&](auto kernel, dim3 grid) {
+        return launch_persistent(kernel, grid, 0, st, G, ghn, hout, d_out, w_hh_t, sync, ring, T, B, H, dbg);
+    };
+    if (form == 0)
+        return with_kbw<1, 2, 4>(nbt, [&](auto N) {
+            return with_kbw<1, 2, 4, 8, 19>(kbw, [&](auto K) { return go(&gru_bwd_persistent_kernel<N, K>, whole); });
+        });
+    if (form == 1)
+        return with_kbw<1, 2>(nbt, [&](auto N) {
+            return with_kbw<1, 2, 4, 8, 19>(kbw, [&](auto K) { return go(&gru_bwd_persistent_p2_kernel<N, K>, halves); });
+        });
+    return with_kbw<1, 2>(nbt, [&](auto N) {
+        return with_kbw<1, 2, 5, 10>(kbw_bf16, [&](auto K) { return go(&gru_bwd_persistent_p2b_kernel<N, K>, halves); });
+    });
 }

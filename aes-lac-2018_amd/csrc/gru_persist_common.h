@@ -264,12 +264,6 @@ __device__ __forceinline__ bool wait_arrivals(unsigned int* shards, int step, in
     }
 }
 
-inline int pick_kbw(int need, const int* opts, int nopts) {
-    for (int i = 0; i < nopts; ++i)
-        if (opts[i] >= need) return opts[i];
-    return -1;
-}
-
 // Co-residency: every workgroup of a persistent launch spins on arrivals from all the others, so the whole grid must be
 // on the chip at once.  The budget is 15/16 of the CURRENT device's compute units (240 of an MI355X's 256: the rest
 // stays free for a concurrent RCCL kernel or the side stream), read once per device; a partitioned (CPX) or smaller
@@ -316,9 +310,30 @@ inline bool grid_is_coresident(K kernel, dim3 grid, size_t lds) {
     return (long)grid.x * grid.y * grid.z <= (long)per_cu * device_cus();
 }
 
+// f(std::integral_constant<int, K>{}) for the smallest K of the ascending list Ks that is >= need (the instantiation a run-time
+// count of k blocks per wave or batch tiles per workgroup runs on); false where none is
+template <int... Ks, typename F>
+inline bool with_kbw(int need, F&& f) {
+    bool ok = false;
+    (void)((need <= Ks && (ok = f(std::integral_constant<int, Ks>{}), true)) || ...);
+    return ok;
+}
+
+// Every persistent launch: the dynamic-LDS attribute where it exceeds the 64 KB default, the co-residency check of THIS
+// instantiation, the launch.  false: the grid is not co-resident (the entry point answers DS2_ERR_UNSUPPORTED).
+template <typename K, typename... Args>
+inline bool launch_persistent(K kernel, dim3 grid, size_t lds, hipStream_t st, Args... args) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return false;
+    if (!grid_is_coresident(kernel, grid, lds)) return false;
+    hipLaunchKernelGGL(kernel, grid, dim3(NWP * 64), lds, st, args...);
+    return true;
+}
+
 }  // namespace
 
-// the 16x16 forms (gru_persist16.hip), launched by the entry points of gru_persist.hip: form 0 = whole batch per workgroup,
+// the 16x16 forms (gru_persist16.hip), launched by the plan switches of gru_persist.hip: form 0 = whole batch per workgroup,
 // 1 = two batch parts (f32-input MFMA), 2 = two batch parts on the bf16 pipe with split operands; nbt = batch tiles of 16 per
 // workgroup (1, 2 or 4 for form 0; 1 or 2 otherwise).  false: the grid is not co-resident (or no such instantiation)
 bool ds2_p16_launch_fwd(int form, int nbt, float* G, float* ghn, float* hout, const float* w_hh, void* sync, float* ring, int T,
