@@ -160,6 +160,11 @@ def build(force=False, verbose=False):
     # (only where the test tree exists and is writable: a packaged / installed tree must still build the product library)
     if os.path.exists(st_src) and os.access(os.path.dirname(st_src), os.W_OK) and (force or _newer(st_src, st_out, [])):
         run([HIPCC, '--offload-arch=gfx950', '-O2', '-shared', '-fPIC', '-o', st_out, st_src])
+    # test infrastructure: the recurrence's gate nonlinearities (__device__ inlines of the headers) behind an elementwise kernel,
+    # compiled with the library's own flags (tests/test_gru_gates_gpu.py)
+    gf_src, gf_out = os.path.join(ROOT, 'tests', 'gate_functions_kernel.hip'), os.path.join(ROOT, 'tests', 'libgate_functions.so')
+    if os.path.exists(gf_src) and os.access(os.path.dirname(gf_src), os.W_OK) and (force or _newer(gf_src, gf_out, deps)):
+        run([HIPCC] + FLAGS + ['-shared', '-o', gf_out, gf_src])
     return OUT
 
 

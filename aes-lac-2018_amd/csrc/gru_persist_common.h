@@ -99,6 +99,10 @@ __device__ __forceinline__ void store_sc1(float* p, float v) {
 
 // Gate nonlinearities on the hardware exp2 / rcp (1 ulp each): the gate math sits on the step's critical path, and the
 // library expf / tanhf / IEEE division cost ~60 more instructions there.  |error| < 3e-7, saturates correctly.
+// Measured on an MI355X against float64 (tests/test_gru_gates_gpu.py: 1.2 M points of [-30, 30], +-[1e-8, 1] log-spaced, +-88,
+// +-100, +-1e4, +-inf, +-0, the largest denormal): max |error| 1.08e-7 (fast_sigmoid, at x = 3.63) and 2.16e-7 (fast_tanh, at
+// x = -1.81), against 9.0e-8 / 7.8e-8 of the step kernels' sigmoidf_ / tanhf; exactly 0 / 1 / +-1 wherever the true value rounds
+// there, monotonic over the sweep, NaN in -> NaN out.
 __device__ __forceinline__ float fast_sigmoid(float x) {
     return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
