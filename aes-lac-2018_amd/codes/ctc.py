@@ -27,6 +27,14 @@ def ctc_costs_and_grad(acts, labels, act_lens, label_lens, grad_scale=1.0, zero_
     labels_c = torch.as_tensor(labels).to('cpu', torch.int32).reshape(-1)
     bsz = label_lens_c.numel()
     max_len = int(label_lens_c.max().item()) if bsz else 0
+    # the kernels index acts and their LDS rows with these values and cannot check them on the device: refuse here
+    if acts.dim() != 3 or bsz != acts.shape[1] or act_lens_c.numel() != bsz:
+        raise ValueError('ctc: acts must be (T, B, A) with B = %d lengths; got acts %s, %d act_lens'
+                         % (bsz, tuple(acts.shape), act_lens_c.numel()))
+    if bsz and (int(label_lens_c.min()) < 0 or int(label_lens_c.sum()) > labels_c.numel()):
+        raise ValueError('ctc: label_lens must be >= 0 and sum to no more than the %d labels given' % labels_c.numel())
+    if labels_c.numel() and not (0 <= int(labels_c.min()) and int(labels_c.max()) < acts.shape[2]):
+        raise ValueError('ctc: labels must lie in 0 .. %d (the alphabet of acts)' % (acts.shape[2] - 1))
     nlab = max(int(labels_c.numel()), 1)
     packed = torch.zeros(nlab + 3 * bsz, dtype=torch.int32)
     packed[:labels_c.numel()] = labels_c

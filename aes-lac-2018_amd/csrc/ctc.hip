@@ -1,12 +1,15 @@
 // CTC negative log-likelihood and its gradient w.r.t. un-normalised activations, gfx950.
 //
 // Three launches:
-//   K0  row log-sum-exp of acts (T*B rows, one wave per row)                      -> lse
+//   K0  row maximum and log1p(sum of exp of the OTHER entries) of acts (T*B rows, one wave per row).  The two parts of the
+//       row's log-sum-exp stay apart so that log p = (a - max) - log1p(..) keeps its RELATIVE accuracy for the symbol a
+//       trained model is sure of: max + log(sum) as one float would round a -log p of 4e-7 to 0 or 1.9e-6 at |a| ~ 20.
 //   K1  grid (B, 2): block (b,0) runs the alpha recursion forward in time, block (b,1) the beta
 //       recursion backward in time, concurrently, in LOG space.  Values are carried in fp64 but the
 //       transcendental part of every log-sum-exp runs in fp32: with m = max(a,b,c),
 //           lse3 = m + log(exp(a-m) + exp(b-m) + exp(c-m)),  the log term lies in [0, log 3],
-//       so its fp32 rounding is ~1e-7 ABSOLUTE whatever |m| is.  (Plain fp32 log space loses ~1e-3
+//       so its fp32 rounding is ~1e-7 ABSOLUTE whatever |m| is; it is formed as log1p of the two smaller terms, so that it
+//       is also accurate RELATIVE to itself when they are tiny (the near-zero cost of a confidently right utterance).  (Plain fp32 log space loses ~1e-3
 //       on the posteriors once |alpha| ~ 2000 at T = 746; a rescaled linear-domain recursion
 //       underflows fp32 when the posterior mass sits far from the row maximum, e.g. early in training
 //       with blank-dominated outputs.)  A row of 2L+1 states lives in LDS (double-buffered, one
@@ -27,37 +30,51 @@ constexpr int MAX_S = 1024;  // 2*L+1 <= 1024
 __device__ __forceinline__ float exp_neg(float x) { return __builtin_amdgcn_exp2f(1.4426950408889634f * x); }
 __device__ __forceinline__ float log_1to3(float s) { return 0.6931471805599453f * __builtin_amdgcn_logf(s); }
 
+// log(1 + x) for x in [0, 2]: the series below 1/64 (next term x^5 / 5: 1e-8 relative), where 1 + x would round x away
+__device__ __forceinline__ float log1p_0to2(float x) {
+    const float small = x * (1.f - x * (0.5f - x * (0.33333334f - x * 0.25f)));
+    return x < 0.015625f ? small : log_1to3(1.f + x);
+}
+
 __device__ __forceinline__ double lse2m(double a, double b) {
     const double m = fmax(a, b);
     if (m == NEG_INF_D) return m;
-    const float s = exp_neg((float)(a - m)) + exp_neg((float)(b - m));
-    return m + (double)log_1to3(s);
+    return m + (double)log1p_0to2(exp_neg((float)(fmin(a, b) - m)));
 }
 __device__ __forceinline__ double lse3m(double a, double b, double c) {
     const double m = fmax(fmax(a, b), c);
     if (m == NEG_INF_D) return m;
-    const float s = exp_neg((float)(a - m)) + exp_neg((float)(b - m)) + exp_neg((float)(c - m));
-    return m + (double)log_1to3(s);
+    const float da = (float)(a - m), db = (float)(b - m), dc = (float)(c - m);      // one of them is 0: the largest term, exp = 1
+    const float lo = fminf(fminf(da, db), dc), mid = __builtin_amdgcn_fmed3f(da, db, dc);
+    return m + (double)log1p_0to2(exp_neg(lo) + exp_neg(mid));
 }
 
 __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ acts, int rows, int A,
-                                                      float* __restrict__ lse) {
+                                                      float* __restrict__ rmx, float* __restrict__ rl1p) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float* p = acts + (size_t)row * A;
     float mx = -INFINITY;
     for (int k = lane; k < A; k += 64) mx = fmaxf(mx, p[k]);
     mx = wave_max(mx);
-    float s = 0.f;
-    for (int k = lane; k < A; k += 64) s += expf(p[k] - mx);
+    float s = 0.f, nmax = 0.f;                          // the entries equal to the maximum are counted, not exponentiated
+    for (int k = lane; k < A; k += 64) {
+        const float v = p[k];
+        if (v == mx) nmax += 1.f;
+        else s += expf(v - mx);
+    }
     s = wave_sum(s);
-    if (lane == 0) lse[row] = mx + logf(s);
+    nmax = wave_sum(nmax);
+    if (lane == 0) {
+        rmx[row] = mx;
+        rl1p[row] = log1pf(s + (nmax - 1.f));
+    }
 }
 
 // One state per thread: NTHR = 256 / 512 / 1024 threads for up to that many states (2 L + 1 of the longest transcript of the
 // minibatch), so a minibatch of short transcripts does not pay the barrier of sixteen waves.
 //
-// Emissions.  State s of frame t needs acts[t][b][ext[s]] - lse[t][b].  Fetched per frame they put a global-memory round
+// Emissions.  State s of frame t needs (acts[t][b][ext[s]] - rmx[t][b]) - rl1p[t][b].  Fetched per frame they put a global-memory round
 // trip on every step of the recursion (round 1-3: a "prefetch" whose subtraction made the compiler wait for it at once, and a
 // vmcnt(0) that also covered the previous frame's alpha / beta store: 0.47 us per frame, 185 us for T = 391).  Now whole
 // frames are staged through LDS, CH at a time: the loads of chunk c + 1 are issued before chunk c's first frame and land in
@@ -68,8 +85,8 @@ constexpr int EM_NLD = 4;                // staging loads per thread and chunk (
 
 template <int NTHR>
 __global__ __launch_bounds__(NTHR) void ctc_alphabeta_kernel(
-    const float* __restrict__ acts, const float* __restrict__ lse, const int32_t* __restrict__ labels,
-    const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ label_lens,
+    const float* __restrict__ acts, const float* __restrict__ rmx, const float* __restrict__ rl1p,
+    const int32_t* __restrict__ labels, const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ label_lens,
     const int32_t* __restrict__ act_lens, int T, int B, int A, int smax, double* __restrict__ alpha,
     double* __restrict__ beta, double* __restrict__ ll_out, float* __restrict__ costs) {
     __shared__ int ext[MAX_S];
@@ -106,9 +123,9 @@ __global__ __launch_bounds__(NTHR) void ctc_alphabeta_kernel(
     const int tstep = dirn == 0 ? 1 : -1;
     if (live) {
         const float* arow = acts + ((size_t)tstart * B + b) * A;
-        const float l0 = lse[(size_t)tstart * B + b];
+        const float m0 = rmx[(size_t)tstart * B + b], p0 = rl1p[(size_t)tstart * B + b];
         const bool on = dirn == 0 ? (s <= 1) : (s >= S - 2);
-        const double v = on ? (double)(arow[sym] - l0) : NEG_INF_D;
+        const double v = on ? (double)((arow[sym] - m0) - p0) : NEG_INF_D;
         rowbuf[0][s + 1] = v;
         out[(size_t)tstart * smax + s] = v;
     }
@@ -123,16 +140,17 @@ __global__ __launch_bounds__(NTHR) void ctc_alphabeta_kernel(
         st_f[i] = (tid < 256 && idx < nper) ? idx / A : -1;
         st_k[i] = idx - (idx / A) * A;
     }
-    float ra[EM_NLD], rl[EM_NLD];
+    float ra[EM_NLD], rl[EM_NLD], rp[EM_NLD];
     auto stage_load = [&](int c) {
 #pragma unroll
         for (int i = 0; i < EM_NLD; ++i) {
-            ra[i] = rl[i] = 0.f;
+            ra[i] = rl[i] = rp[i] = 0.f;
             const int n = 1 + c * CH + st_f[i];
             if (st_f[i] >= 0 && n < tl) {
                 const size_t row = (size_t)(tstart + tstep * n) * B + b;
                 ra[i] = acts[row * A + st_k[i]];
-                rl[i] = lse[row];
+                rl[i] = rmx[row];
+                rp[i] = rl1p[row];
             }
         }
     };
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(NTHR) void ctc_alphabeta_kernel(
             if (st_f[i] >= 0) {
                 float a = ra[i];
                 asm volatile("" : "+v"(a));      // keeps the subtraction (and with it the wait for the loads) HERE, at the chunk's
-                dst[tid + 256 * i] = a - rl[i];  // last frame: hoisted in front of the frame loop it would wait at the chunk's first
+                dst[tid + 256 * i] = (a - rl[i]) - rp[i];  // last frame: hoisted in front of the frame loop it would wait at the chunk's first
             }
     };
     if (nchunk > 0) {
@@ -182,7 +200,8 @@ __global__ __launch_bounds__(NTHR) void ctc_alphabeta_kernel(
     }
 }
 
-__global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__ acts, const float* __restrict__ lse,
+__global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__ acts, const float* __restrict__ rmx,
+                                                       const float* __restrict__ rl1p,
                                                        const int32_t* __restrict__ labels,
                                                        const int32_t* __restrict__ label_offsets,
                                                        const int32_t* __restrict__ label_lens,
@@ -214,17 +233,17 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
     const int L = label_lens[b], S = 2 * L + 1;
     const int32_t* lab = labels + label_offsets[b];
     const float* arow = acts + ((size_t)t * B + b) * A;
-    const float l0 = lse[(size_t)t * B + b];
+    const float m0 = rmx[(size_t)t * B + b], p0 = rl1p[(size_t)t * B + b];
     const double* al = alpha + ((size_t)b * T + t) * smax;
     const double* be = beta + ((size_t)b * T + t) * smax;
-    const double base_blank = ll + (double)(arow[0] - l0);
+    const double base_blank = ll + (double)((arow[0] - m0) - p0);
     float blank_sum = 0.f;
     for (int s = tid; s < S; s += 128) {
         const double ab = al[s] + be[s];
         if (ab == NEG_INF_D) continue;
         if (s & 1) {
             const int k = lab[s >> 1];
-            atomicAdd(&occ[k], expf((float)(ab - ll - (double)(arow[k] - l0))));
+            atomicAdd(&occ[k], expf((float)(ab - ll - (double)((arow[k] - m0) - p0))));
         } else {
             blank_sum += expf((float)(ab - base_blank));
         }
@@ -232,7 +251,7 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
     blank_sum = wave_sum(blank_sum);
     if ((tid & 63) == 0) atomicAdd(&occ[0], blank_sum);
     __syncthreads();
-    for (int k = tid; k < A; k += 128) grow[k] = grad_scale * (expf(arow[k] - l0) - occ[k]);
+    for (int k = tid; k < A; k += 128) grow[k] = grad_scale * (expf((arow[k] - m0) - p0) - occ[k]);
 }
 
 }  // namespace
@@ -240,7 +259,7 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
 extern "C" size_t ds2_ctc_ws_bytes(int T, int B, int A, int max_label_len) {
     (void)A;
     const size_t smax = 2 * (size_t)max_label_len + 1;
-    return sizeof(double) * (2 * (size_t)B * T * smax + (size_t)B) + sizeof(float) * (size_t)T * B + 64;
+    return sizeof(double) * (2 * (size_t)B * T * smax + (size_t)B) + sizeof(float) * 2 * (size_t)T * B + 64;
 }
 
 extern "C" int ds2_ctc_loss_grad(const float* acts, const int32_t* labels, const int32_t* label_offsets,
@@ -256,16 +275,17 @@ extern "C" int ds2_ctc_loss_grad(const float* acts, const int32_t* labels, const
     double* alpha = (double*)ws;
     double* beta = alpha + (size_t)B * T * smax;
     double* ll = beta + (size_t)B * T * smax;
-    float* lse = (float*)(ll + B);
-    hipLaunchKernelGGL(ctc_lse_kernel, dim3(ds2_cdiv((long)T * B, 4)), dim3(256), 0, st, acts, T * B, A, lse);
+    float* rmx = (float*)(ll + B);
+    float* rl1p = rmx + (size_t)T * B;
+    hipLaunchKernelGGL(ctc_lse_kernel, dim3(ds2_cdiv((long)T * B, 4)), dim3(256), 0, st, acts, T * B, A, rmx, rl1p);
 #define DS2_CTC_AB(N_)                                                                                                  \
-    hipLaunchKernelGGL(ctc_alphabeta_kernel<N_>, dim3(B, 2), dim3(N_), 0, st, acts, lse, labels, label_offsets,          \
+    hipLaunchKernelGGL(ctc_alphabeta_kernel<N_>, dim3(B, 2), dim3(N_), 0, st, acts, rmx, rl1p, labels, label_offsets,    \
                        label_lens, act_lens, T, B, A, smax, alpha, beta, ll, costs)
     if (smax <= 256) DS2_CTC_AB(256);
     else if (smax <= 512) DS2_CTC_AB(512);
     else DS2_CTC_AB(1024);
 #undef DS2_CTC_AB
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(128), 0, st, acts, lse, labels, label_offsets, label_lens,
+    hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(128), 0, st, acts, rmx, rl1p, labels, label_offsets, label_lens,
                        act_lens, T, B, A, smax, alpha, beta, ll, grad_scale, zero_batch_if_inf, grad);
     DS2_CHECK_LAUNCH();
     return DS2_OK;

@@ -101,6 +101,75 @@ def ctc_loss_and_grad(acts, labels, act_lens, label_lens, blank=0):
     return costs, grad
 
 
+def _lse_rows(stack):
+    """log-sum-exp over axis 0 of (n, S) float64 with -inf entries allowed; all -inf gives -inf."""
+    m = stack.max(axis=0)
+    safe = np.where(m > -np.inf, m, 0.0)
+    with np.errstate(divide='ignore'):
+        return np.where(m > -np.inf, safe + np.log(np.exp(stack - safe).sum(axis=0)), -np.inf)
+
+
+def ctc_loss_and_grad_fast(acts, labels, act_lens, label_lens, blank=0):
+    """``ctc_loss_and_grad`` restated with the states of a frame as one numpy vector (one Python loop over t per utterance):
+    the same float64 recursion, the same conventions (blank, +inf cost and zero gradient when infeasible, the tl = 0 rule),
+    fast enough for training-size batches (T = 746, L = 511 in ~0.05 s).  tests/test_ctc_ref_cpu.py ties it to the loop
+    version, to ``ctc_brute_force`` and to torch's ctc_loss in float64."""
+    acts = np.asarray(acts, dtype=np.float64)
+    t_max, bsz, nalpha = acts.shape
+    logp = _log_softmax(acts)
+    grad = np.zeros_like(acts)
+    costs = np.zeros(bsz, dtype=np.float64)
+    off = 0
+    neg_inf = -np.inf
+    for b in range(bsz):
+        tl = int(act_lens[b])
+        ll = int(label_lens[b])
+        lab = np.asarray(labels[off:off + ll], dtype=np.int64)
+        off += ll
+        s_len = 2 * ll + 1
+        ext = np.full(s_len, blank, dtype=np.int64)
+        ext[1::2] = lab
+        if tl == 0:
+            costs[b] = 0.0 if ll == 0 else np.inf
+            continue
+        lp = logp[:tl, b, :]
+        em = lp[:, ext]                                                   # (tl, S): log p of each state's symbol
+        skip = np.zeros(s_len, dtype=bool)                                # state s may be entered from s - 2
+        skip[2:] = (ext[2:] != blank) & (ext[2:] != ext[:-2])
+        skip_b = np.zeros(s_len, dtype=bool)                              # state s may be entered from s + 2 (beta)
+        skip_b[:-2] = (ext[:-2] != blank) & (ext[:-2] != ext[2:])
+        alpha = np.full((tl, s_len), neg_inf)
+        beta = np.full((tl, s_len), neg_inf)
+        alpha[0, :2] = em[0, :2]
+        stack = np.full((3, s_len), neg_inf)
+        for t in range(1, tl):
+            prev = alpha[t - 1]
+            stack[0] = prev
+            stack[1, 1:] = prev[:-1]
+            stack[2, 2:] = np.where(skip[2:], prev[:-2], neg_inf)
+            alpha[t] = _lse_rows(stack) + em[t]
+        beta[tl - 1, -2:] = em[tl - 1, -2:]
+        stack = np.full((3, s_len), neg_inf)
+        for t in range(tl - 2, -1, -1):
+            nxt = beta[t + 1]
+            stack[0] = nxt
+            stack[1, :-1] = nxt[1:]
+            stack[2, :-2] = np.where(skip_b[:-2], nxt[2:], neg_inf)
+            beta[t] = _lse_rows(stack) + em[t]
+        ll_total = float(_lse_rows(alpha[tl - 1, -2:].reshape(-1, 1))[0])
+        costs[b] = -ll_total
+        if ll_total == neg_inf:
+            continue
+        ab = alpha + beta
+        with np.errstate(invalid='ignore'):
+            post = np.where(ab > neg_inf, np.exp(ab - ll_total - em), 0.0)   # (tl, S)
+        occ = np.zeros((tl, nalpha))
+        for k in np.unique(ext):
+            occ[:, k] = post[:, ext == k].sum(axis=1)
+        grad[:tl, b, :] = np.exp(lp) - occ
+    return costs, grad
+
+
 def ctc_brute_force(acts_tb, label, blank=0):
     """-log p(label | acts) by enumerating every length-T path (tiny T, A only)."""
     acts_tb = np.asarray(acts_tb, dtype=np.float64)
