@@ -62,14 +62,16 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
         mx = fmaxf(mx, v[i]);
     }
     mx = wave_max(mx);
-    float sum = 0.f;
+    // the denominator in fp64: an fp32 tree of 9 additions left a row's outputs summing to 1 only within ~6e-7 (5.8 * 2^-24
+    // measured at A = 129); now a row sum is off by the rounding of `inv` and of the products alone (<= 2 * 2^-24)
+    double sum = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         v[i] = (lane + 64 * i < A) ? expf(v[i] - mx) : 0.f;
-        sum += v[i];
+        sum += (double)v[i];
     }
-    sum = wave_sum(sum);
-    const float inv = 1.f / sum;
+    sum = wave_sum_d(sum);
+    const float inv = (float)(1.0 / sum);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int k = lane + 64 * i;
@@ -77,7 +79,15 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     }
 }
 
-// argmax with ties -> lowest index (torch.max semantics); one wave per row
+// does candidate (v, k) beat (best, bi)?  torch.max order: NaN is the largest value, equal values -> lowest index
+__device__ __forceinline__ bool argmax_takes(float v, int k, float best, int bi) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || k < bi);
+    return v > best || (v == best && k < bi);
+}
+
+// argmax with ties -> lowest index, NaN -> the first NaN (torch.max semantics); one wave per row.  A lane without a column
+// keeps (-inf, INT_MAX), which loses to every real column: the index written is always in [0, A).
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int rows, int A,
                                                           int32_t* __restrict__ idx) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -88,7 +98,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     int bi = 0x7fffffff;
     for (int k = lane; k < A; k += 64) {
         const float v = p[k];
-        if (v > best || (v == best && k < bi)) {
+        if (argmax_takes(v, k, best, bi)) {
             best = v;
             bi = k;
         }
@@ -97,7 +107,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        const bool take = (ov > best) || (ov == best && oi < bi);
+        const bool take = argmax_takes(ov, oi, best, bi);
         if (take) {
             best = ov;
             bi = oi;

@@ -289,7 +289,8 @@ int ds2_gru_bidir_bwd_persistent_dh(float* G, float* ghn, const float* hout, con
 
 /* ------------------------------------------------------------------ output head helpers
  * softmax over the last dim of (rows, A) (eval branch, codes/model.py:204-205) and the argmax
- * of GreedyDecoder.decode (codes/decoder.py:154; ties -> lowest index). */
+ * of GreedyDecoder.decode (codes/decoder.py:154; ties -> lowest index, NaN counts as the largest value and the first
+ * one wins, as torch.max: the index is always in [0, A)). */
 int ds2_softmax_rows(const float* x, int rows, int A, float* y, void* stream);
 int ds2_argmax_rows(const float* x, int rows, int A, int32_t* idx, void* stream);
 /* greedy collapse on device: best (B,T) int32 (batch-major), sizes (B) -> out_ids (B,T) and
