@@ -81,6 +81,8 @@ SIGNATURES = {
     'ds2_ctc_beam_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_beam_search_batch': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F,
                                        _P, _Z, _P, _P, _P, _P, _P, _P]),
+    'ds2_ctc_align_ws_bytes': (_Z, [_I, _I, _I]),
+    'ds2_ctc_align': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 404            # DS2_ABI_VERSION of include/ds2hip.h: the revision this table (and ops.py) is written against

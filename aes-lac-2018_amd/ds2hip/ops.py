@@ -639,6 +639,27 @@ def ctc_beam_search(probs, sizes, beam_width, blank=0, log_input=False, lm=None,
     return labels, offsets, lens, score, ctc
 
 
+def ctc_align(probs, sizes, labels, label_offsets, label_lens, max_label_len, blank=0, log_input=False):
+    """CTC forced alignment of a batch in one launch on the current stream (``ds2_ctc_align``).  probs (B,T,A) fp32 on the
+    device; sizes (B,), flat labels, label_offsets (B,), label_lens (B,) int32 on the device.  Returns the device tensors
+    states (B,T), starts, ends (B,max_label_len) int32 and score (B,) fp32; an utterance without an alignment has
+    score -inf and -1 everywhere."""
+    for x in (probs, sizes, labels, label_offsets, label_lens):
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+    bsz, t, a = probs.shape
+    max_label_len = int(max_label_len)
+    ws_bytes = lib.query('ds2_ctc_align_ws_bytes', bsz, t, max_label_len)
+    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
+    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
+    ends = torch.empty_like(starts)
+    score = _empty((bsz,), probs)
+    lib.call('ds2_ctc_align', probs, sizes, labels, label_offsets, label_lens, bsz, t, a, max_label_len, int(blank),
+             int(bool(log_input)), ws, ws.numel(), states, starts, ends, score)
+    return states, starts, ends, score
+
+
 # ----------------------------------------------------------------------------- CTC
 def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_len, grad_scale=1.0,
                   zero_batch_if_inf=False):

@@ -331,6 +331,28 @@ int ds2_ctc_beam_search_batch(const float* probs, const int32_t* sizes, int B, i
                               size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
                               float* out_score, float* out_ctc_logp, void* stream);
 
+/* ------------------------------------------------------------------ CTC forced alignment (csrc/ctc_align.hip)
+ * Not in the reference.  One launch finds, for every utterance of a batch, the single best alignment (max-sum / Viterbi) of
+ * its KNOWN transcript to frames 0 .. sizes[b]-1, over the extended sequence blank, l1, blank, ..., lL, blank (state s:
+ * even = blank, odd = label s/2) with the CTC transitions stay, s-1, and s-2 onto a label that differs from the one at s-2;
+ * the path starts in state 0 or 1 and ends in state 2L or 2L-1.  probs (B,T,A) and sizes (B) as for the beam search (sizes
+ * clamped to 0..T; nothing past sizes[b] is read, padding may hold NaN); labels / label_offsets / label_lens as for
+ * ds2_ctc_loss_grad.  The per-frame term is the input (log_input = 1) or its fp32 log (log_input = 0, log 0 = -inf); a NaN
+ * counts as -inf; path scores are carried in fp64.  Ties: at each (t, s) stay wins, then s-1, then s-2; at the end state 2L
+ * wins over 2L-1 -- so a result is bit-reproducible and does not depend on the rest of the batch.
+ * max_label_len >= every label_lens[b], <= 511 (one state per thread; longer is DS2_ERR_ARG); A <= 256.
+ * ws >= ds2_ctc_align_ws_bytes(B, T, max_label_len) bytes (one back-pointer byte per frame and state; need not be zeroed).
+ * Outputs: states (B,T) int32 the state index per frame, -1 from sizes[b] on; starts / ends (B,max_label_len) int32 the
+ * first and last frame (inclusive) spent in each label's state, -1 past label_lens[b]; score (B) the path's log-score.
+ * No alignment (more labels plus adjacent repeats than frames, every path -inf, a label id outside [0, A) or equal to
+ * blank, a label_lens[b] outside 0..max_label_len -- checked on the device): score = -inf and states / starts / ends all -1.
+ * An empty transcript gives the all-blank path.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+size_t ds2_ctc_align_ws_bytes(int B, int T, int max_label_len);
+int ds2_ctc_align(const float* probs, const int32_t* sizes, const int32_t* labels, const int32_t* label_offsets,
+                  const int32_t* label_lens, int B, int T, int A, int max_label_len, int blank, int log_input, void* ws,
+                  size_t ws_bytes, int32_t* states, int32_t* starts, int32_t* ends, float* score, void* stream);
+
 /* ------------------------------------------------------------------ CTC
  * Replaces warpctc_pytorch.CTCLoss (train.py:179, codes/engine.py:22, codes/metrics.py:51):
  * softmax over A inside, blank 0, costs[b] = -log p(labels_b | acts[:act_lens[b], b]),
