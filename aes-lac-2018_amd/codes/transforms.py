@@ -58,17 +58,23 @@ class BatchSpectrogram(object):
     clip's frames, percentage = T_i / float(T_max) stored as float32.
     """
 
-    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None):
+    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None):
         self.normalize, self.eps, self.device = normalize, eps, device
         self.scale = ops.amplitude_scale(scale)      # int16 clips (RawAudioBatch) come out as q * scale: see ToTensor
+        self.noise = noise                           # a NoiseInjection: the bank the drawn noise of a batch is mixed from
 
     def __call__(self, wavs, offsets=None):
         if isinstance(wavs, RawAudioBatch):                  # int16 clips (+ drawn augmentation): decode on the device
+            if wavs.noise is not None and self.noise is None:
+                raise RuntimeError('the batch carries noise draws (ToTensor(noise=...)) but this BatchSpectrogram was '
+                                   'built without a noise bank: pass noise=<the NoiseInjection> to it')
             if wavs.ready is not None:               # uploaded ahead of time on the prefetcher's copy stream
                 torch.cuda.current_stream().wait_event(wavs.ready)
                 wavs.pcm.record_stream(torch.cuda.current_stream())
             pcm = wavs.pcm if wavs.pcm.is_cuda else wavs.pcm.to(self.device, non_blocking=True)
             flat, offs = ops.decode_augment(pcm, wavs.offsets, wavs.tempos, wavs.gains_db, scale=self.scale)
+            if wavs.noise is not None:               # noise drawn by the loader: mixed in place, between gain and the STFT
+                self.noise.mix_batch(flat, offs, wavs.noise, self.scale)
             lens = [offs[i + 1] - offs[i] for i in range(len(offs) - 1)]
         elif offsets is None:
             lens = [int(w.numel()) for w in wavs]
@@ -105,12 +111,13 @@ class Compose(object):
 
 class PCMClip(object):
     """What a loader worker hands on for one utterance: the int16 samples as read from the file plus the augmentation
-    DRAWN for it (tempo factor, gain in dB; None = no augmentation).  The arithmetic -- int16 -> float, WSOLA tempo,
-    gain, 16-bit requantisation -- happens on the GPU after collate (``ds2hip.ops.decode_augment``)."""
-    __slots__ = ('pcm', 'tempo', 'gain_db')
+    DRAWN for it (tempo factor, gain in dB; None = no augmentation; ``noise``: what ``NoiseInjection.draw`` returned).  The
+    arithmetic -- int16 -> float, WSOLA tempo, gain, 16-bit requantisation, noise mixing -- happens on the GPU after collate
+    (``ds2hip.ops.decode_augment``, ``ds2hip.ops.noise_mix``)."""
+    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise')
 
-    def __init__(self, pcm, tempo=None, gain_db=None):
-        self.pcm, self.tempo, self.gain_db = pcm, tempo, gain_db
+    def __init__(self, pcm, tempo=None, gain_db=None, noise=None):
+        self.pcm, self.tempo, self.gain_db, self.noise = pcm, tempo, gain_db, noise
 
     def numel(self):
         return int(self.pcm.numel())
@@ -118,10 +125,11 @@ class PCMClip(object):
 
 class RawAudioBatch(object):
     """A collated minibatch of ``PCMClip``s: ONE int16 buffer (page-locked when the DataLoader pins) + clip offsets +
-    the per-clip augmentation parameters.  2 bytes per sample cross PCIe; everything else happens on the device."""
+    the per-clip augmentation parameters.  2 bytes per sample cross PCIe; everything else happens on the device.
+    ``noise``: the clips' ``NoiseInjection.draw`` results (None for a clip without noise), or None when no clip drew any."""
 
-    def __init__(self, pcm, offsets, tempos=None, gains_db=None):
-        self.pcm, self.offsets, self.tempos, self.gains_db = pcm, list(offsets), tempos, gains_db
+    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None):
+        self.pcm, self.offsets, self.tempos, self.gains_db, self.noise = pcm, list(offsets), tempos, gains_db, noise
         self.ready = None                            # event recorded behind an asynchronous upload (DevicePrefetcher)
 
     @classmethod
@@ -133,7 +141,8 @@ class RawAudioBatch(object):
         aug = any(c.tempo is not None or c.gain_db is not None for c in clips)
         tempos = [1.0 if c.tempo is None else float(c.tempo) for c in clips] if aug else None
         gains = [0.0 if c.gain_db is None else float(c.gain_db) for c in clips] if aug else None
-        return cls(pcm, offs, tempos, gains)
+        noise = [c.noise for c in clips] if any(c.noise is not None for c in clips) else None
+        return cls(pcm, offs, tempos, gains, noise)
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -143,7 +152,8 @@ class RawAudioBatch(object):
         return self
 
     def to(self, device, non_blocking=False):
-        out = RawAudioBatch(self.pcm.to(device, non_blocking=non_blocking), self.offsets, self.tempos, self.gains_db)
+        out = RawAudioBatch(self.pcm.to(device, non_blocking=non_blocking), self.offsets, self.tempos, self.gains_db,
+                            self.noise)
         return out
 
 
@@ -155,7 +165,9 @@ class ToTensor(object):
     only READS the file's int16 samples and DRAWS (tempo, gain) exactly as the reference does (``np.random.uniform``,
     tempo first): with ``defer=True`` (what the training loader uses) it returns a ``PCMClip`` and the decode + WSOLA
     tempo + gain + 16-bit requantisation run on the GPU for the whole minibatch after collate; with ``defer=False``
-    (the reference's per-clip contract) the same kernels run at once and a 1-D float tensor comes back.  There is no
+    (the reference's per-clip contract) the same kernels run at once and a 1-D float tensor comes back.  ``noise`` (a
+    ``NoiseInjection``, default None) adds its draw behind the two above -- nothing is drawn without it, so a seeded run
+    without noise keeps its tempo / gain sequence -- and the clip's noise is mixed by the same device stage.  There is no
     host implementation in the product; ``oracle/audio.py`` specifies the arithmetic (sox itself is absent from the
     reference tree, so the tempo change is the published WSOLA algorithm with sox's defaults, not sox's samples).
 
@@ -170,10 +182,11 @@ class ToTensor(object):
     ``num_workers=0``."""
 
     def __init__(self, sample_rate=16000, augment=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), defer=False,
-                 device='cuda', scale=None):
+                 device='cuda', scale=None, noise=None):
         self.sample_rate, self.augment = sample_rate, augment
         self.tempo_range, self.gain_range = tempo_range, gain_range
         self.defer, self.device = defer, device
+        self.noise = noise
         self.scale = ops.amplitude_scale(scale)
 
     def _load(self, path):
@@ -192,6 +205,8 @@ class ToTensor(object):
         if self.augment:
             clip.tempo = float(np.random.uniform(low=self.tempo_range[0], high=self.tempo_range[1]))
             clip.gain_db = float(np.random.uniform(low=self.gain_range[0], high=self.gain_range[1]))
+        if self.noise is not None:
+            clip.noise = self.noise.draw()
         if self.defer:
             return clip
         if torch.utils.data.get_worker_info() is not None:
@@ -199,13 +214,184 @@ class ToTensor(object):
                                'build the transform with defer=True (the minibatch is then decoded on the device after '
                                'collate) or use num_workers=0')
         batch = RawAudioBatch.from_clips([clip]).to(self.device)
-        wav, _ = ops.decode_augment(batch.pcm, batch.offsets, batch.tempos, batch.gains_db, self.sample_rate,
-                                    scale=self.scale)
+        wav, offs = ops.decode_augment(batch.pcm, batch.offsets, batch.tempos, batch.gains_db, self.sample_rate,
+                                       scale=self.scale)
+        if batch.noise is not None:
+            self.noise.mix_batch(wav, offs, batch.noise, self.scale)
         return wav.cpu()
 
     def __repr__(self):
         return '{}(sample_rate={}, augment={}, tempo_range={}, gain_range={})'.format(
             self.__class__.__name__, self.sample_rate, self.augment, self.tempo_range, self.gain_range)
+
+
+def noise_start(u, noise_len, n):
+    """First sample of the noise crop for a clip of ``n`` samples, from the uniform draw ``u`` in [0, 1): the reference's
+    ``torch.rand(()) * (noise_len - signal_len)`` in samples when the recording is at least as long as the clip (the crop
+    then ends inside it); any position of the recording, which then repeats, when it is shorter.  Always in [0, noise_len)."""
+    noise_len, n = int(noise_len), int(n)
+    if noise_len >= n:
+        return max(0, min(int(float(u) * (noise_len - n)), noise_len - n, noise_len - 1))
+    return max(0, min(int(float(u) * noise_len), noise_len - 1))
+
+
+class NoiseInjection(object):
+    """Additive background noise at a random level (reference ``codes/transforms.py:227-292``).
+
+    The reference's class cannot run: ``noise.size`` is a method, so the energy line raises (:268-269); ``prob`` is
+    documented but neither stored nor applied; ``__repr__`` reads attributes that were never set; a noise file shorter than
+    the clip fails the crop.  This is its evident intent, every decision written down:
+
+    * ``path`` is searched recursively for ``.wav`` files, in sorted order (a missing directory raises ``IOError``, as in
+      the reference).  Every file must be 16-bit mono PCM at ``sample_rate``: the reference resamples and downmixes through
+      sox, which is not available here, so any other file is REFUSED by name -- convert the noise set once, offline.  An
+      empty directory and a zero-length file are refused; a set longer than ``max_bank_seconds`` (one hour = 115 MB of
+      int16 per GPU) raises ``ValueError`` rather than being truncated.
+    * with probability ``prob`` a clip gets noise.  ``draw()`` -- what a loader worker calls -- returns None or
+      ``(file index, level, u)`` from, in this order, ``np.random.binomial(1, prob)`` and then, only on a hit,
+      ``np.random.choice(n_files)``, ``np.random.uniform(*noise_levels)`` and ``torch.rand(())``: the last three are the
+      reference's own draws in its order (:257-262); the binomial in front is how the torchaudio fork the reference credits
+      applied ``prob`` -- from recollection, that code is not in the reference tree.
+    * the crop starts at ``noise_start(u, noise_len, n)`` once the clip's length after the tempo change is known; a
+      recording shorter than the clip repeats.
+    * ``out = x + level * rms(x) / rms(noise) * noise`` (the reference's formula with the rms its ancestor computes,
+      ``sqrt(dot / size)``); a silent crop (or clip) adds nothing.  The sum is returned as floats, not requantised to 16 bit.
+
+    The arithmetic is one device launch for a whole minibatch (``ds2hip.ops.noise_mix``): the recordings live on the GPU as
+    one int16 bank, uploaded on first use in the process that owns the GPU (never in a loader worker; the workers only
+    know the files' lengths).  ``ToTensor(noise=...)`` attaches the draw to its clip and ``BatchSpectrogram(noise=...)``
+    mixes after decode, tempo and gain.  ``__call__(x)`` keeps the reference's per-clip contract through the same kernel
+    (a CPU tensor makes a GPU round trip); ``scale`` is the amplitude contract of the waveform it is given
+    (``ops.amplitude_scale``: the noise goes through the same conversion as the speech)."""
+
+    def __init__(self, path, sample_rate=16000, noise_levels=(0, 0.5), prob=0.4, device='cuda', max_bank_seconds=3600,
+                 scale=None):
+        import os
+        import threading
+        import wave
+        if path is None or not os.path.isdir(path):
+            raise IOError('Directory does not exist: {}'.format(path))
+        self.path, self.sample_rate, self.prob = path, int(sample_rate), float(prob)
+        self.noise_levels = (float(noise_levels[0]), float(noise_levels[1]))
+        self.device, self.max_bank_seconds = device, max_bank_seconds
+        self.scale = ops.amplitude_scale(scale)
+        self.paths = sorted(os.path.join(d, f) for d, _, files in os.walk(path) for f in files
+                            if f.lower().endswith('.wav'))
+        if not self.paths:
+            raise ValueError('no .wav file under the noise directory {}'.format(path))
+        self.lengths = []
+        for p in self.paths:
+            try:
+                with wave.open(p, 'rb') as w:
+                    rate, width, chans, frames = w.getframerate(), w.getsampwidth(), w.getnchannels(), w.getnframes()
+            except (wave.Error, EOFError) as e:
+                raise ValueError('noise file {} is not a PCM WAV file: {}'.format(p, e))
+            if rate != self.sample_rate or width != 2 or chans != 1:
+                raise ValueError('noise file {}: {} Hz, {} bit, {} channel(s); the noise bank takes 16-bit mono PCM at {} Hz '
+                                 'only (nothing is resampled here: convert the file)'.format(p, rate, 8 * width, chans,
+                                                                                            self.sample_rate))
+            if frames <= 0:
+                raise ValueError('noise file {} holds no samples'.format(p))
+            self.lengths.append(int(frames))
+        total = sum(self.lengths)
+        if total > max_bank_seconds * self.sample_rate:
+            raise ValueError('the noise files under {} hold {:.1f} s of audio, more than max_bank_seconds = {} (the bank lives '
+                             'on the GPU, 2 bytes per sample; nothing is truncated: raise the limit or thin the set)'.format(
+                                 path, total / float(self.sample_rate), max_bank_seconds))
+        self.starts = [0]
+        for n in self.lengths[:-1]:
+            self.starts.append(self.starts[-1] + n)
+        self._banks, self._lock = {}, threading.Lock()
+
+    def __getstate__(self):                          # (a spawned loader worker gets the description, never the device bank)
+        state = dict(self.__dict__)
+        state['_banks'], state['_lock'] = {}, None
+        return state
+
+    def __setstate__(self, state):
+        import threading
+        self.__dict__.update(state)
+        self._lock = threading.Lock()
+
+    def draw(self, rng=None):
+        """None (no noise for this clip) or ``(file index, level, u)``.  ``rng`` (a ``numpy.random.RandomState`` or
+        ``Generator``) replaces the global ``np.random`` -- and ``torch.rand`` for ``u`` -- when given."""
+        import numpy as np
+        r = np.random if rng is None else rng
+        if not r.binomial(1, self.prob):
+            return None
+        index = int(r.choice(len(self.paths)))
+        level = float(r.uniform(*self.noise_levels))
+        u = float(torch.rand(())) if rng is None else float(r.uniform(0.0, 1.0))
+        return index, level, u
+
+    def bank(self, device=None):
+        """The int16 samples of every file, concatenated in listing order, on ``device``: read and uploaded on first use."""
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('the noise bank lives on the GPU and cannot be used in a DataLoader worker process; let the '
+                               'worker draw (ToTensor(noise=..., defer=True)) and mix after collate (BatchSpectrogram(noise=...))')
+        device = torch.device(self.device if device is None else device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        with self._lock:
+            bank = self._banks.get(device)
+            if bank is None:
+                loader = ToTensor(sample_rate=self.sample_rate)
+                parts = [loader._load(p) for p in self.paths]
+                for p, part, n in zip(self.paths, parts, self.lengths):
+                    if part.numel() != n:
+                        raise ValueError('noise file {} holds {} samples, its header says {}'.format(p, part.numel(), n))
+                bank = self._banks[device] = torch.cat(parts).to(device)
+        return bank
+
+    def params(self, draws, lens):
+        """Per-clip (noise_lo, noise_len, noise_start, levels) for ``ops.noise_mix`` from the clips' draws and lengths."""
+        lo, ln, st, lv = [], [], [], []
+        for d, n in zip(draws, lens):
+            if d is None:
+                lo.append(0), ln.append(0), st.append(0), lv.append(0.0)
+                continue
+            index, level, u = d
+            lo.append(self.starts[index]), ln.append(self.lengths[index]), lv.append(float(level))
+            st.append(noise_start(u, self.lengths[index], n))
+        return lo, ln, st, lv
+
+    def mix_batch(self, flat, offsets, draws, scale, return_coef=False):
+        """Mix the drawn noise into the flat float clips IN PLACE, one launch pair on the current stream."""
+        lens = [offsets[i + 1] - offsets[i] for i in range(len(offsets) - 1)]
+        lo, ln, st, lv = self.params(draws, lens)
+        return ops.noise_mix(flat, offsets, self.bank(flat.device), lo, ln, st, lv, scale, out=flat,
+                             return_coef=return_coef)
+
+    def __call__(self, x):
+        """x: 1-D float tensor of samples -> the same clip with (probability ``prob``) noise added, on x's device."""
+        assert isinstance(x, torch.Tensor) and x.dim() == 1, 'Only mono audio is accepted'
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('NoiseInjection mixes on the GPU and cannot run in a DataLoader worker process; let the '
+                               'worker draw (ToTensor(noise=..., defer=True)) and mix after collate, or use num_workers=0')
+        draw = self.draw()
+        if draw is None or x.numel() == 0:
+            return x
+        src = x.device
+        wav = x.to(self.device, torch.float32).contiguous()
+        if wav.data_ptr() == x.data_ptr():
+            wav = wav.clone()
+        self.mix_batch(wav, [0, wav.numel()], [draw], self.scale)
+        return wav.to(src)
+
+    def __repr__(self):
+        return '{}({}, sample_rate={}, noise_levels={}, prob={}, files={}, seconds={:.1f})'.format(
+            self.__class__.__name__, self.path, self.sample_rate, self.noise_levels, self.prob, len(self.paths),
+            sum(self.lengths) / float(self.sample_rate))
+
+
+def waveform_noise(transform):
+    """The ``NoiseInjection`` whose draws the ``ToTensor`` stage of ``transform`` attaches to its clips (None when there is
+    none): what the ``BatchSpectrogram`` that decodes those clips must be built with."""
+    for t in getattr(transform, 'transforms', [transform]):
+        if isinstance(t, ToTensor):
+            return t.noise
+    return None
 
 
 def waveform_scale(transform):

@@ -96,7 +96,7 @@ def load_model(model_path, num_classes=29, return_transforms=False, data_dir=Non
     model.load_state_dict(ckpt['state_dict'])
     out = [model]
     if return_transforms:
-        out += list(tu.get_default_transforms(data_dir or args.data_dir, args.config))
+        out += list(tu.get_default_transforms(data_dir or args.data_dir, args.config, noise=False))   # (evaluation: no noise)
     if return_ckpt:
         out.append(ckpt)
     return out[0] if len(out) == 1 else tuple(out)

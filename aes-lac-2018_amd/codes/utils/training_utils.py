@@ -2,7 +2,8 @@
 
 Config schema (unchanged): ``model{name, langs, freeze_layers, map_fc, params}``,
 ``training{num_epochs, batch_size, max_norm, augment, finetune}``, ``optimizer{name, params, per_layer_lr}``,
-``scheduler{name, params}``.  Broken branches of the reference are implemented to their evident intent
+``scheduler{name, params}``.  Additions: ``training.audio_scale`` (``audio_scale``) and the optional block
+``training.noise{path, noise_levels, prob}`` (``get_noise``).  Broken branches of the reference are implemented to their evident intent
 (SURVEY.md section 4): ``langs[0]`` is the fine-tune target language, the new FC layer's *weight* is
 normally initialised.
 """
@@ -21,15 +22,24 @@ LOG = logging.getLogger('aes-lac-2018')
 NUM_CLASSES = {'pt_BR': 43, 'en': 29}
 
 
-def get_default_transforms(data_dir, config, gpu_frontend=True):
+def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     """Waveform loader (+ per-utterance spectrogram when ``gpu_frontend`` is False) and one ToLabel per language
-    (training_utils.py:18-34).  With ``gpu_frontend`` the spectrogram runs batched on the device after collate."""
+    (training_utils.py:18-34).  With ``gpu_frontend`` the spectrogram runs batched on the device after collate.
+    ``training.noise`` of the config (``get_noise``) reaches the TRAINING transform only: its ``ToTensor`` draws the noise
+    (``transforms.waveform_noise(train_t)`` is what the training ``BatchSpectrogram`` is built with), or, without
+    ``gpu_frontend``, the ``NoiseInjection`` stands between the loader and the spectrogram as in the reference.
+    ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at the block."""
     augment = bool(config.training.get('augment', False))       # tempo + gain on the training set only
     # gpu_frontend: workers hand on int16 clips + the drawn (tempo, gain); decode, WSOLA, gain and the spectrogram all run
     # on the device after collate.  Otherwise the reference's per-utterance contract (each transform returns a tensor).
     tail = [] if gpu_frontend else [transforms.ToSpectrogram(librosa_compat=True)]
     scale = audio_scale(config)
-    train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=gpu_frontend, scale=scale)] + tail)
+    bank = get_noise(data_dir, config, scale) if noise else None
+    if gpu_frontend:
+        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=True, scale=scale, noise=bank)])
+    else:
+        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=False, scale=scale)] +
+                                     ([bank] if bank is not None else []) + tail)
     val_t = transforms.Compose([transforms.ToTensor(augment=False, defer=gpu_frontend, scale=scale)] + tail)
     target_t = [transforms.ToLabel(os.path.join(data_dir, 'labels.{}.json'.format(lang)), lang=lang,
                                    remove_accents=(lang != 'pt_BR')) for lang in config.model.langs]
@@ -42,6 +52,22 @@ def audio_scale(config):
     contract of the waveform loader (``transforms.ToTensor``)."""
     training = config.get('training', {}) if hasattr(config, 'get') else {}
     return (training or {}).get('audio_scale', None)
+
+
+def get_noise(data_dir, config, scale=None):
+    """``training.noise`` of the JSON config (an addition to the reference's schema, whose NoiseInjection no config reaches):
+    ``{"path": DIR, "noise_levels": [lo, hi], "prob": p}`` -> a ``transforms.NoiseInjection`` (None without the block).
+    Independent of ``training.augment``; a relative ``path`` that does not exist from the working directory is looked up
+    under ``--data-dir``.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""
+    training = config.get('training', {}) if hasattr(config, 'get') else {}
+    block = (training or {}).get('noise', None)
+    if not block:
+        return None
+    unknown = set(block) - {'path', 'noise_levels', 'prob', 'max_bank_seconds'}
+    if unknown or 'path' not in block:
+        raise ValueError('training.noise takes path (required), noise_levels, prob, max_bank_seconds; got %s' % sorted(block))
+    kwargs = {k: block[k] for k in ('noise_levels', 'prob', 'max_bank_seconds') if k in block}
+    return transforms.NoiseInjection(_resolve(block['path'], data_dir), scale=scale, **kwargs)
 
 
 def is_multitask(config):

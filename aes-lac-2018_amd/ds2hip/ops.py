@@ -133,6 +133,58 @@ def decode_augment(pcm, offsets, tempos=None, gains_db=None, sample_rate=16000, 
     return wav, list(offsets)
 
 
+NOISE_CHUNK = 4096                      # DS2_NOISE_CHUNK of include/ds2hip.h: samples per workgroup of ds2_noise_mix
+
+
+def noise_mix(wav, offsets, bank, noise_lo, noise_len, noise_start, levels, noise_scale, out=None, return_coef=False,
+              ws=None):
+    """Additive background noise for a minibatch in one launch pair on the current stream (``ds2_noise_mix``).
+    wav: the flat float clips ``decode_augment`` returns, offsets: its python list (B+1).  bank: every noise recording's
+    int16 samples concatenated on the device; per clip (python sequences of length B) ``noise_lo`` / ``noise_len`` the
+    recording (length 0 = no noise for this clip), ``noise_start`` the first sample of the crop, ``levels`` the drawn level.
+    Returns the mixed flat buffer (``out``, which may be ``wav`` itself; a new tensor when None), and the per-clip
+    coefficients (B,) float32 on the device with ``return_coef``.  ``ws``: a caller's uint8 workspace of at least
+    ``ds2_noise_mix_ws_bytes`` bytes (its contents do not matter); allocated here when None."""
+    import numpy as np
+    bsz = len(offsets) - 1
+    if not (wav.is_cuda and bank.is_cuda) or wav.dtype != torch.float32 or bank.dtype != torch.int16:
+        raise RuntimeError('noise_mix takes a float32 waveform buffer and an int16 noise bank, both on the device')
+    off = np.asarray(offsets, np.int64)
+    lo, ln, st = (np.asarray(v, np.int64).reshape(-1) for v in (noise_lo, noise_len, noise_start))
+    lv = np.asarray(levels, np.float32).reshape(-1)
+    if not (len(lo) == len(ln) == len(st) == len(lv) == bsz >= 1):
+        raise ValueError('noise_mix: one (noise_lo, noise_len, noise_start, level) per clip, got %d / %d / %d / %d for %d clips'
+                         % (len(lo), len(ln), len(st), len(lv), bsz))
+    if off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > wav.numel():
+        raise ValueError('noise_mix: offsets do not describe clips inside the waveform buffer')
+    drawn = ln > 0
+    if (ln < 0).any() or (lo[drawn] < 0).any() or (lo[drawn] + ln[drawn] > bank.numel()).any():
+        raise ValueError('noise_mix: a noise recording lies outside the bank (%d samples)' % bank.numel())
+    if ((st[drawn] < 0) | (st[drawn] >= ln[drawn])).any():
+        raise ValueError('noise_mix: noise_start must lie inside its recording')
+    if not np.isfinite(lv).all():
+        raise ValueError('noise_mix: noise levels must be finite')
+    # one upload: the four int64 arrays, then the float levels viewed as int64 pairs
+    lv_pad = np.zeros(2 * ((bsz + 1) // 2), np.float32)
+    lv_pad[:bsz] = lv
+    meta_d = upload_small(torch.from_numpy(np.concatenate([off, lo, ln, st, lv_pad.view(np.int64)])), wav.device)
+    a = bsz + 1
+    ws_bytes = lib.query('ds2_noise_mix_ws_bytes', bsz, int(np.diff(off).max()))
+    if ws is None:
+        ws = torch.empty((int(ws_bytes),), dtype=torch.uint8, device=wav.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < ws_bytes:
+        raise ValueError('noise_mix: the workspace must be uint8 of at least %d bytes' % ws_bytes)
+    if out is None:
+        out = torch.empty_like(wav)
+        if off[0] > 0 or off[-1] < wav.numel():          # (samples outside every clip pass through)
+            out.copy_(wav)
+    coef = _empty((bsz,), wav) if return_coef else None
+    lib.call('ds2_noise_mix', wav, meta_d[:a], bsz, bank, meta_d[a:a + bsz], meta_d[a + bsz:a + 2 * bsz],
+             meta_d[a + 2 * bsz:a + 3 * bsz], meta_d[a + 3 * bsz:].view(torch.float32), float(noise_scale), out, coef, ws,
+             int(ws_bytes))
+    return (out, coef) if return_coef else out
+
+
 # ----------------------------------------------------------------------------- small host <-> device transfers
 class _PinnedRing(object):
     """A few reusable page-locked staging buffers per dtype: ``tensor.pin_memory()`` allocates page-locked memory

@@ -86,6 +86,36 @@ int ds2_wsola_tempo(const float* x, const int64_t* in_offsets, const int64_t* ou
 int ds2_gain_requantize(const float* x, const int64_t* offsets, const float* gain, int B, float out_scale, float* out,
                         void* stream);
 
+/* ------------------------------------------------------------------ noise injection
+ * Stands where NoiseInjection.__call__ would run (codes/transforms.py:254-287), between the waveform loader and the
+ * spectrogram: additive background noise at a drawn level relative to the clip's rms.  The reference's class raises on its
+ * first call (`noise.size` is a method, :268-269), so this is its evident intent; one launch pair mixes the whole minibatch.
+ *   wav, offsets   clip b = wav[offsets[b] .. offsets[b+1]), n_b samples: the float output of the decode above
+ *   bank           the int16 samples of every noise recording, concatenated; clip b's recording is
+ *                  bank[noise_lo[b] .. noise_lo[b] + noise_len[b]).  noise_len[b] == 0: no noise drawn for this clip --
+ *                  out equals wav bit for bit there and coef[b] = 0
+ *   noise_start    first sample of the crop, in [0, noise_len[b]) (clamped into it; nothing outside the recording is read)
+ *   level          (B) float, the drawn noise level
+ * For i in [0, n_b):  nz[i] = (float)bank[noise_lo + (noise_start + i) mod noise_len] * noise_scale (one rounded multiply, as
+ * ds2_pcm16_to_float; a recording shorter than the clip repeats);  Ex = sum wav[i]^2, En = sum nz[i]^2 in float64 over exact
+ * products;  coef = (float)(level * sqrt(Ex / n) / sqrt(En / n)) -- the reference's noise_level * signal_energy /
+ * noise_energy with rms energies -- and 0 when En == 0 (a silent crop) or the quotient is not finite;
+ * out[i] = wav[i] + coef * nz[i], the product and the sum each rounded once (no fma).  coef == 0 copies wav (bit for bit).
+ * out == wav (in place) is allowed.  coef (B floats) may be NULL.
+ * Two kernels: per-chunk (Ex, En) partials into ws (DS2_NOISE_CHUNK samples per workgroup, chunks counted from the clip's own
+ * start), then every workgroup sums its clip's partials in index order and mixes its chunk.  No atomics: a clip's output
+ * bits do not depend on its position in the batch, on the other clips, on its offset in wav, or on what ws held.
+ * ws >= ds2_noise_mix_ws_bytes(B, longest clip) bytes, need not be zeroed; ws_bytes fixes the grid (ws_bytes / (16 B) chunks
+ * per clip; the workgroups of a longer clip take several chunks each, so every sample is still mixed) and must hold at
+ * least one partial per clip.  B in 1..65535; noise_scale > 0 (the frontend's amplitude scale: the ratio of the energies
+ * cancels it, but the noise goes through the same conversion as the speech).
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_NOISE_CHUNK 4096
+size_t ds2_noise_mix_ws_bytes(int B, size_t max_clip_len);
+int ds2_noise_mix(const float* wav, const int64_t* offsets, int B, const int16_t* bank, const int64_t* noise_lo,
+                  const int64_t* noise_len, const int64_t* noise_start, const float* level, float noise_scale, float* out,
+                  float* coef, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ generic fp32 GEMM (MFMA)
  * C[M,N] = op(A) * op(B) + beta * C, row-major with leading dimensions.  op(A)=A (M x K, lda) or
  * A^T (A stored K x M); op(B)=B (K x N, ldb) or B^T (B stored N x K).  beta is 0 or 1.
