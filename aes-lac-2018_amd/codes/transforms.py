@@ -58,16 +58,22 @@ class BatchSpectrogram(object):
     clip's frames, percentage = T_i / float(T_max) stored as float32.
     """
 
-    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None):
+    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None, spec_augment=None):
         self.normalize, self.eps, self.device = normalize, eps, device
         self.scale = ops.amplitude_scale(scale)      # int16 clips (RawAudioBatch) come out as q * scale: see ToTensor
         self.noise = noise                           # a NoiseInjection: the bank the drawn noise of a batch is mixed from
+        self.spec_augment = spec_augment             # a SpecAugment: resolves and applies the draws a batch carries
 
     def __call__(self, wavs, offsets=None):
+        spec = None
         if isinstance(wavs, RawAudioBatch):                  # int16 clips (+ drawn augmentation): decode on the device
             if wavs.noise is not None and self.noise is None:
                 raise RuntimeError('the batch carries noise draws (ToTensor(noise=...)) but this BatchSpectrogram was '
                                    'built without a noise bank: pass noise=<the NoiseInjection> to it')
+            spec = wavs.spec
+            if spec is not None and self.spec_augment is None:
+                raise RuntimeError('the batch carries SpecAugment draws (ToTensor(spec_augment=...)) but this '
+                                   'BatchSpectrogram was built without one: pass spec_augment=<the SpecAugment> to it')
             if wavs.ready is not None:               # uploaded ahead of time on the prefetcher's copy stream
                 torch.cuda.current_stream().wait_event(wavs.ready)
                 wavs.pcm.record_stream(torch.cuda.current_stream())
@@ -91,6 +97,8 @@ class BatchSpectrogram(object):
         t_max = max(frames)
         # (the offsets stay on the host, in page-locked memory the two kernels read in place: ops.spectrogram)
         inputs = ops.spectrogram(flat, torch.tensor(offs, dtype=torch.int64), t_max, self.normalize, self.eps)
+        if spec is not None:                         # masks (+ warp) drawn by the loader: one launch behind the normalisation
+            inputs = self.spec_augment.apply_batch(inputs, frames, spec)
         pct = torch.tensor([f / float(t_max) for f in frames], dtype=torch.float32)
         return inputs, pct
 
@@ -111,13 +119,14 @@ class Compose(object):
 
 class PCMClip(object):
     """What a loader worker hands on for one utterance: the int16 samples as read from the file plus the augmentation
-    DRAWN for it (tempo factor, gain in dB; None = no augmentation; ``noise``: what ``NoiseInjection.draw`` returned).  The
-    arithmetic -- int16 -> float, WSOLA tempo, gain, 16-bit requantisation, noise mixing -- happens on the GPU after collate
-    (``ds2hip.ops.decode_augment``, ``ds2hip.ops.noise_mix``)."""
-    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise')
+    DRAWN for it (tempo factor, gain in dB; None = no augmentation; ``noise``: what ``NoiseInjection.draw`` returned;
+    ``spec``: what ``SpecAugment.draw`` returned).  The arithmetic -- int16 -> float, WSOLA tempo, gain, 16-bit
+    requantisation, noise mixing, and behind the spectrogram the SpecAugment masks -- happens on the GPU after collate
+    (``ds2hip.ops.decode_augment``, ``ds2hip.ops.noise_mix``, ``ds2hip.ops.spec_augment``)."""
+    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise', 'spec')
 
-    def __init__(self, pcm, tempo=None, gain_db=None, noise=None):
-        self.pcm, self.tempo, self.gain_db, self.noise = pcm, tempo, gain_db, noise
+    def __init__(self, pcm, tempo=None, gain_db=None, noise=None, spec=None):
+        self.pcm, self.tempo, self.gain_db, self.noise, self.spec = pcm, tempo, gain_db, noise, spec
 
     def numel(self):
         return int(self.pcm.numel())
@@ -126,10 +135,12 @@ class PCMClip(object):
 class RawAudioBatch(object):
     """A collated minibatch of ``PCMClip``s: ONE int16 buffer (page-locked when the DataLoader pins) + clip offsets +
     the per-clip augmentation parameters.  2 bytes per sample cross PCIe; everything else happens on the device.
-    ``noise``: the clips' ``NoiseInjection.draw`` results (None for a clip without noise), or None when no clip drew any."""
+    ``noise``: the clips' ``NoiseInjection.draw`` results (None for a clip without noise), or None when no clip drew any;
+    ``spec``: the same for ``SpecAugment.draw``."""
 
-    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None):
+    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None, spec=None):
         self.pcm, self.offsets, self.tempos, self.gains_db, self.noise = pcm, list(offsets), tempos, gains_db, noise
+        self.spec = spec
         self.ready = None                            # event recorded behind an asynchronous upload (DevicePrefetcher)
 
     @classmethod
@@ -142,7 +153,8 @@ class RawAudioBatch(object):
         tempos = [1.0 if c.tempo is None else float(c.tempo) for c in clips] if aug else None
         gains = [0.0 if c.gain_db is None else float(c.gain_db) for c in clips] if aug else None
         noise = [c.noise for c in clips] if any(c.noise is not None for c in clips) else None
-        return cls(pcm, offs, tempos, gains, noise)
+        spec = [c.spec for c in clips] if any(c.spec is not None for c in clips) else None
+        return cls(pcm, offs, tempos, gains, noise, spec)
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -153,7 +165,7 @@ class RawAudioBatch(object):
 
     def to(self, device, non_blocking=False):
         out = RawAudioBatch(self.pcm.to(device, non_blocking=non_blocking), self.offsets, self.tempos, self.gains_db,
-                            self.noise)
+                            self.noise, self.spec)
         return out
 
 
@@ -167,7 +179,10 @@ class ToTensor(object):
     tempo + gain + 16-bit requantisation run on the GPU for the whole minibatch after collate; with ``defer=False``
     (the reference's per-clip contract) the same kernels run at once and a 1-D float tensor comes back.  ``noise`` (a
     ``NoiseInjection``, default None) adds its draw behind the two above -- nothing is drawn without it, so a seeded run
-    without noise keeps its tempo / gain sequence -- and the clip's noise is mixed by the same device stage.  There is no
+    without noise keeps its tempo / gain sequence -- and the clip's noise is mixed by the same device stage.
+    ``spec_augment`` (a ``SpecAugment``, default None) adds ITS draw behind the noise draw, under the same rule, and the clip
+    carries it to the ``BatchSpectrogram``: it needs ``defer=True`` (a waveform cannot carry a draw; in a per-clip pipeline
+    the object itself stands behind ``ToSpectrogram``, where ``get_default_transforms`` puts it).  There is no
     host implementation in the product; ``oracle/audio.py`` specifies the arithmetic (sox itself is absent from the
     reference tree, so the tempo change is the published WSOLA algorithm with sox's defaults, not sox's samples).
 
@@ -182,11 +197,15 @@ class ToTensor(object):
     ``num_workers=0``."""
 
     def __init__(self, sample_rate=16000, augment=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), defer=False,
-                 device='cuda', scale=None, noise=None):
+                 device='cuda', scale=None, noise=None, spec_augment=None):
         self.sample_rate, self.augment = sample_rate, augment
         self.tempo_range, self.gain_range = tempo_range, gain_range
         self.defer, self.device = defer, device
         self.noise = noise
+        if spec_augment is not None and not defer:
+            raise ValueError('ToTensor(spec_augment=...) needs defer=True: the draw travels with the clip to the '
+                             'BatchSpectrogram; in a per-clip pipeline put the SpecAugment behind ToSpectrogram')
+        self.spec_augment = spec_augment
         self.scale = ops.amplitude_scale(scale)
 
     def _load(self, path):
@@ -207,6 +226,8 @@ class ToTensor(object):
             clip.gain_db = float(np.random.uniform(low=self.gain_range[0], high=self.gain_range[1]))
         if self.noise is not None:
             clip.noise = self.noise.draw()
+        if self.spec_augment is not None:
+            clip.spec = self.spec_augment.draw()
         if self.defer:
             return clip
         if torch.utils.data.get_worker_info() is not None:
@@ -383,6 +404,130 @@ class NoiseInjection(object):
         return '{}({}, sample_rate={}, noise_levels={}, prob={}, files={}, seconds={:.1f})'.format(
             self.__class__.__name__, self.path, self.sample_rate, self.noise_levels, self.prob, len(self.paths),
             sum(self.lengths) / float(self.sample_rate))
+
+
+class SpecAugment(object):
+    """SpecAugment (Park et al. 2019) on the log-spectrogram: a time warp, ``freq_masks`` frequency masks and ``time_masks``
+    time masks per clip.  The reference has nothing of the kind -- its augmentation is tempo, gain and noise, all on the
+    waveform -- so every rule here is a decision (README "SpecAugment").  The defaults are the paper's, which were defined on
+    80 mel bins; here they meet 161 linear bins, and nobody has measured their effect on WER in this model.
+
+    * with probability ``prob`` a clip is augmented.  ``draw()`` -- what a loader worker calls; it knows neither the GPU nor
+      the clip's length -- returns None or a tuple of uniform variates from, in this order, ``np.random.binomial(1, prob)``
+      and then, only on a hit, ONE ``np.random.uniform(0, 1, size=n)`` with n = 2 [time_warp > 0] + 2 freq_masks +
+      2 time_masks: warp (centre, shift), every frequency mask (width, start), every time mask (width, start).
+    * ``params(draws, frames)`` resolves them once the clip's frame count T is known (after the tempo change); every
+      floor(u k) is clamped to k - 1.  Frequency: f = floor(u (freq_width + 1)), f0 = floor(u' (161 - f + 1)).  Time:
+      cap = min(time_width, floor(time_ratio T)), t = floor(u (cap + 1)), t0 = floor(u' (T - t + 1)).  Warp, W = time_warp,
+      only when T > 2 W (the identity otherwise): c = W + floor(u (T - 2 W)), c2 = c + floor(u' (2 W + 1)) - W -- source
+      frame c lands on output frame c2, both halves resampled linearly.  A None draw is the identity warp and no mask.
+    * masked cells are SET to ``mask_value`` (0 = the clip's mean after the frontend's normalisation).
+
+    ``ToTensor(spec_augment=...)`` attaches the draw to its clip and ``BatchSpectrogram(spec_augment=...)`` applies the
+    batch's draws in one launch behind the spectrogram (``ds2hip.ops.spec_augment``; in place when ``time_warp == 0``).
+    ``__call__(spect)`` is the per-clip contract through the same kernel (a CPU tensor makes a GPU round trip)."""
+
+    def __init__(self, freq_masks=2, freq_width=27, time_masks=2, time_width=100, time_ratio=0.2, time_warp=0, prob=1.0,
+                 mask_value=0.0, device='cuda'):
+        def whole(name, v, lo, hi=None):
+            if isinstance(v, bool) or int(v) != v or v < lo or (hi is not None and v > hi):
+                raise ValueError('SpecAugment: %s must be an integer %s, got %r'
+                                 % (name, 'in %d..%d' % (lo, hi) if hi is not None else '>= %d' % lo, v))
+            return int(v)
+        self.freq_masks = whole('freq_masks', freq_masks, 0, ops.SPEC_MAX_MASKS)
+        self.freq_width = whole('freq_width', freq_width, 0, NBINS)
+        self.time_masks = whole('time_masks', time_masks, 0, ops.SPEC_MAX_MASKS)
+        self.time_width = whole('time_width', time_width, 0)
+        self.time_warp = whole('time_warp', time_warp, 0)
+        for name, v in (('time_ratio', time_ratio), ('prob', prob)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError('SpecAugment: %s must lie in [0, 1], got %r' % (name, v))
+        self.time_ratio, self.prob, self.mask_value, self.device = float(time_ratio), float(prob), float(mask_value), device
+
+    def draw(self, rng=None):
+        """None (this clip stays as it is) or the clip's uniform variates.  ``rng`` (a ``numpy.random.RandomState`` or
+        ``Generator``) replaces the global ``np.random`` when given."""
+        import numpy as np
+        r = np.random if rng is None else rng
+        if not r.binomial(1, self.prob):
+            return None
+        n = 2 * (self.time_warp > 0) + 2 * self.freq_masks + 2 * self.time_masks
+        return tuple(float(u) for u in r.uniform(0, 1, size=n))
+
+    def params(self, draws, frames):
+        """(warp, fmask, tmask) for ``ops.spec_augment`` from the clips' draws and frame counts: python lists of shape
+        (B, 2), (B, freq_masks, 2), (B, time_masks, 2); warp is None when ``time_warp == 0``."""
+        import math
+
+        def fl(u, k):                                # floor(u k) for u in [0, 1), never k itself
+            return min(int(math.floor(float(u) * k)), k - 1)
+        w = self.time_warp
+        warp, fmask, tmask = ([] if w > 0 else None), [], []
+        for d, t_b in zip(draws, frames):
+            t_b = int(t_b)
+            if d is None:
+                if w > 0:
+                    warp.append([0, 0])
+                fmask.append([[0, 0]] * self.freq_masks), tmask.append([[0, 0]] * self.time_masks)
+                continue
+            u = list(d)
+            if w > 0:
+                uc, us = u[0], u[1]
+                u = u[2:]
+                if t_b > 2 * w:
+                    c = w + fl(uc, t_b - 2 * w)
+                    warp.append([c, c + fl(us, 2 * w + 1) - w])
+                else:
+                    warp.append([0, 0])
+            row = []
+            for m in range(self.freq_masks):
+                f = fl(u[2 * m], self.freq_width + 1)
+                row.append([fl(u[2 * m + 1], NBINS - f + 1), f])
+            fmask.append(row)
+            u = u[2 * self.freq_masks:]
+            cap = min(self.time_width, int(math.floor(self.time_ratio * t_b)))
+            row = []
+            for m in range(self.time_masks):
+                t = fl(u[2 * m], cap + 1)
+                row.append([fl(u[2 * m + 1], t_b - t + 1), t])
+            tmask.append(row)
+        return warp, fmask, tmask
+
+    def apply_batch(self, inputs, frames, draws):
+        """Apply the clips' draws to ``inputs`` (B, t_max, 161) on the device, one launch on the current stream: in place
+        when ``time_warp == 0``, into a new tensor otherwise.  Returns the tensor that holds the result."""
+        warp, fmask, tmask = self.params(draws, frames)
+        return ops.spec_augment(inputs, frames, warp, fmask, tmask, self.mask_value)
+
+    def __call__(self, spect):
+        """spect: (T, 161) float tensor -> the augmented spectrogram (probability ``prob``), on spect's device."""
+        assert isinstance(spect, torch.Tensor) and spect.dim() == 2 and spect.shape[1] == NBINS, 'expected (T, 161)'
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('SpecAugment masks on the GPU and cannot run in a DataLoader worker process; let the worker '
+                               'draw (ToTensor(spec_augment=..., defer=True)) and mask after collate '
+                               '(BatchSpectrogram(spec_augment=...)), or use num_workers=0')
+        draw = self.draw()
+        if draw is None or spect.shape[0] == 0:
+            return spect
+        src = spect.device
+        x = spect.to(self.device, torch.float32).contiguous()
+        if x.data_ptr() == spect.data_ptr():
+            x = x.clone()                            # (the caller's tensor is not written)
+        return self.apply_batch(x.unsqueeze(0), [x.shape[0]], [draw])[0].to(src)
+
+    def __repr__(self):
+        return ('{}(freq_masks={}, freq_width={}, time_masks={}, time_width={}, time_ratio={}, time_warp={}, prob={}, '
+                'mask_value={})').format(self.__class__.__name__, self.freq_masks, self.freq_width, self.time_masks,
+                                         self.time_width, self.time_ratio, self.time_warp, self.prob, self.mask_value)
+
+
+def waveform_spec_augment(transform):
+    """The ``SpecAugment`` whose draws the ``ToTensor`` stage of ``transform`` attaches to its clips (None when there is
+    none): what the ``BatchSpectrogram`` that decodes those clips must be built with."""
+    for t in getattr(transform, 'transforms', [transform]):
+        if isinstance(t, ToTensor):
+            return t.spec_augment
+    return None
 
 
 def waveform_noise(transform):

@@ -3,7 +3,7 @@
 Config schema (unchanged): ``model{name, langs, freeze_layers, map_fc, params}``,
 ``training{num_epochs, batch_size, max_norm, augment, finetune}``, ``optimizer{name, params, per_layer_lr}``,
 ``scheduler{name, params}``.  Additions: ``training.audio_scale`` (``audio_scale``) and the optional block
-``training.noise{path, noise_levels, prob}`` (``get_noise``).  Broken branches of the reference are implemented to their evident intent
+``training.noise{path, noise_levels, prob}`` (``get_noise``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
 (SURVEY.md section 4): ``langs[0]`` is the fine-tune target language, the new FC layer's *weight* is
 normally initialised.
 """
@@ -28,18 +28,23 @@ def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     ``training.noise`` of the config (``get_noise``) reaches the TRAINING transform only: its ``ToTensor`` draws the noise
     (``transforms.waveform_noise(train_t)`` is what the training ``BatchSpectrogram`` is built with), or, without
     ``gpu_frontend``, the ``NoiseInjection`` stands between the loader and the spectrogram as in the reference.
-    ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at the block."""
+    ``training.spec_augment`` (``get_spec_augment``) travels the same way: the training ``ToTensor`` draws
+    (``transforms.waveform_spec_augment(train_t)`` is what the training ``BatchSpectrogram`` is built with), or, without
+    ``gpu_frontend``, the ``SpecAugment`` stands behind the spectrogram.
+    ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at either block."""
     augment = bool(config.training.get('augment', False))       # tempo + gain on the training set only
     # gpu_frontend: workers hand on int16 clips + the drawn (tempo, gain); decode, WSOLA, gain and the spectrogram all run
     # on the device after collate.  Otherwise the reference's per-utterance contract (each transform returns a tensor).
     tail = [] if gpu_frontend else [transforms.ToSpectrogram(librosa_compat=True)]
     scale = audio_scale(config)
     bank = get_noise(data_dir, config, scale) if noise else None
+    spec = get_spec_augment(config) if noise else None
     if gpu_frontend:
-        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=True, scale=scale, noise=bank)])
+        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=True, scale=scale, noise=bank,
+                                                          spec_augment=spec)])
     else:
         train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=False, scale=scale)] +
-                                     ([bank] if bank is not None else []) + tail)
+                                     ([bank] if bank is not None else []) + tail + ([spec] if spec is not None else []))
     val_t = transforms.Compose([transforms.ToTensor(augment=False, defer=gpu_frontend, scale=scale)] + tail)
     target_t = [transforms.ToLabel(os.path.join(data_dir, 'labels.{}.json'.format(lang)), lang=lang,
                                    remove_accents=(lang != 'pt_BR')) for lang in config.model.langs]
@@ -68,6 +73,26 @@ def get_noise(data_dir, config, scale=None):
         raise ValueError('training.noise takes path (required), noise_levels, prob, max_bank_seconds; got %s' % sorted(block))
     kwargs = {k: block[k] for k in ('noise_levels', 'prob', 'max_bank_seconds') if k in block}
     return transforms.NoiseInjection(_resolve(block['path'], data_dir), scale=scale, **kwargs)
+
+
+SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'time_warp', 'prob', 'mask_value')
+
+
+def get_spec_augment(config):
+    """``training.spec_augment`` of the JSON config (an addition to the reference's schema): a block whose keys are
+    ``transforms.SpecAugment``'s keyword names -> that object; keys left out keep the constructor's defaults (``{}`` is all
+    defaults), an unknown key is refused by name, and None comes back without the block.  Independent of
+    ``training.augment`` and ``training.noise``.  The block is saved with the checkpoint's ``args``; nothing reads it at
+    test time."""
+    training = config.get('training', {}) if hasattr(config, 'get') else {}
+    block = (training or {}).get('spec_augment', None)
+    if block is None:
+        return None
+    unknown = sorted(set(block) - set(SPEC_AUGMENT_KEYS))
+    if unknown:
+        raise ValueError('training.spec_augment: unknown key(s) %s; it takes %s' % (', '.join(unknown),
+                                                                                   ', '.join(SPEC_AUGMENT_KEYS)))
+    return transforms.SpecAugment(**{k: block[k] for k in SPEC_AUGMENT_KEYS if k in block})
 
 
 def is_multitask(config):

@@ -185,6 +185,81 @@ def noise_mix(wav, offsets, bank, noise_lo, noise_len, noise_start, levels, nois
     return (out, coef) if return_coef else out
 
 
+SPEC_MAX_MASKS = 8                      # masks of one kind per clip ds2_spec_augment takes
+SPEC_MAX_WARP_FRAMES = 4096             # with a warp: frame products stay exact in float (include/ds2hip.h)
+
+
+def _spec_table(name, table, shape):
+    """A per-clip table given as a list or a tensor -> int32 numpy of ``shape`` (one -1 allowed; None or empty: no entries)."""
+    import numpy as np
+    if isinstance(table, torch.Tensor):
+        table = table.detach().cpu().numpy()
+    arr = np.asarray([] if table is None else table)
+    if arr.size == 0:
+        arr = np.zeros([0 if d == -1 else d for d in shape], np.int64)
+    if not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError('spec_augment: %s must hold integers, got %s' % (name, arr.dtype))
+    try:
+        arr = arr.astype(np.int64).reshape(shape)
+    except ValueError:
+        raise ValueError('spec_augment: %s has shape %s, expected %s' % (name, arr.shape, tuple(shape)))
+    if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+        raise ValueError('spec_augment: %s does not fit 32-bit integers' % name)
+    return np.ascontiguousarray(arr, np.int32)
+
+
+def spec_augment(x, frames, warp=None, fmask=None, tmask=None, mask_value=0.0, out=None):
+    """SpecAugment for a minibatch in one launch on the current stream (``ds2_spec_augment``).
+    x: (B, t_max, 161) float32 on the device, what ``spectrogram`` returns; frames: the clips' valid frames (B).  Per clip
+    (python lists or tensors of integers): ``warp`` (B, 2) = (c, c2), source frame c lands on output frame c2 (c2 == c: not
+    warped), or None; ``fmask`` (B, MF, 2) = (f0, f) and ``tmask`` (B, MT, 2) = (t0, t), start and width (width 0: no mask;
+    masks are clamped to the clip), MF, MT <= 8, or None.  Masked cells become ``mask_value``; frames past a clip's own are 0.
+    Without a warp the masks are stored IN PLACE (``out`` None or ``x``: x is returned); with a warp, or with another ``out``,
+    every cell of ``out`` (allocated here when None; never ``x``) is written.  Returns the tensor that holds the result."""
+    import numpy as np
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3 or \
+            x.shape[2] != F_BINS or not x.is_contiguous():
+        raise RuntimeError('spec_augment takes a contiguous float32 (B, t_max, %d) tensor on the device' % F_BINS)
+    bsz, t_max = int(x.shape[0]), int(x.shape[1])
+    if bsz < 1 or t_max < 1:
+        raise ValueError('spec_augment: an empty batch')
+    fr = _spec_table('frames', frames, (bsz,))
+    if (fr < 1).any() or (fr > t_max).any():
+        raise ValueError('spec_augment: every clip has 1..t_max = %d frames, got %s' % (t_max, fr.tolist()))
+    parts = [fr]
+    if warp is not None:
+        wp = _spec_table('warp', warp, (bsz, 2))
+        if (fr > SPEC_MAX_WARP_FRAMES).any():
+            raise ValueError('spec_augment: a time warp takes clips of at most %d frames, got %d'
+                             % (SPEC_MAX_WARP_FRAMES, int(fr.max())))
+        if (wp < 0).any() or (wp >= fr[:, None]).any():
+            raise ValueError('spec_augment: warp (c, c2) must lie inside the clip, 0 <= c, c2 < frames')
+        parts.append(wp.reshape(-1))
+    fm, tm = _spec_table('fmask', fmask, (bsz, -1, 2)), _spec_table('tmask', tmask, (bsz, -1, 2))
+    n_f, n_t = fm.shape[1], tm.shape[1]
+    if n_f > SPEC_MAX_MASKS or n_t > SPEC_MAX_MASKS:
+        raise ValueError('spec_augment: %d frequency and %d time masks per clip, at most %d of a kind are taken'
+                         % (n_f, n_t, SPEC_MAX_MASKS))
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous()):
+        raise ValueError('spec_augment: out must be a contiguous tensor like x')
+    in_place = warp is None and (out is None or out.data_ptr() == x.data_ptr())
+    if in_place:
+        out = x
+        if n_f == 0 and n_t == 0:
+            return out                                   # nothing to do
+    elif out is None:
+        out = torch.empty_like(x)
+    elif out.data_ptr() == x.data_ptr():
+        raise ValueError('spec_augment: a time warp cannot work in place, out must be another tensor than x')
+    # one upload: frames, then warp, fmask, tmask (int32 each)
+    meta_d = upload_small(torch.from_numpy(np.concatenate(parts + [fm.reshape(-1), tm.reshape(-1)])), x.device)
+    a = bsz + (2 * bsz if warp is not None else 0)
+    lib.call('ds2_spec_augment', x, out, bsz, t_max, meta_d[:bsz], meta_d[bsz:a] if warp is not None else None,
+             meta_d[a:a + 2 * bsz * n_f] if n_f else None, n_f,
+             meta_d[a + 2 * bsz * n_f:] if n_t else None, n_t, float(mask_value))
+    return out
+
+
 # ----------------------------------------------------------------------------- small host <-> device transfers
 class _PinnedRing(object):
     """A few reusable page-locked staging buffers per dtype: ``tensor.pin_memory()`` allocates page-locked memory

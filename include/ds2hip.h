@@ -116,6 +116,41 @@ int ds2_noise_mix(const float* wav, const int64_t* offsets, int B, const int16_t
                   const int64_t* noise_len, const int64_t* noise_start, const float* level, float noise_scale, float* out,
                   float* coef, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ SpecAugment
+ * Time warp, frequency masks and time masks on the log-spectrogram of a minibatch, one launch, between ds2_spectrogram_fwd and
+ * the model.  The reference has no such stage (its augmentation is tempo, gain and noise, all on the waveform): nothing here is
+ * parity, every rule is a decision written down below.
+ *   x, out         (B, t_max, 161) float32, the layout ds2_spectrogram_fwd writes
+ *   frames         (B) int32: T_b, the clip's valid frames, 1 <= T_b <= t_max (clamped into [0, t_max])
+ *   warp           (B, 2) int32: c, c2, both in [0, T_b) (clamped into it) -- or NULL: no clip is warped
+ *   fmask, MF      (B, MF, 2) int32: f0, f -- bins [f0, f0 + f) of every valid frame; width f <= 0: no mask
+ *   tmask, MT      (B, MT, 2) int32: t0, t -- frames [t0, t0 + t); width t <= 0: no mask
+ * Time warp (only with warp != NULL): source frame c lands on output frame c2 and both halves are resampled linearly along
+ * time.  For output frame t < c2: num = t * c, den = c2, base = 0; for t >= c2: num = (t - c2) * (T_b - c), den = T_b - c2,
+ * base = c.  i0 = base + num / den (integer division), frac = (float)(num % den) / (float)den (one correctly rounded division
+ * of two integers below 2^24), i1 = min(i0 + 1, T_b - 1), and y[t][k] = fmaf(frac, x[i1][k] - x[i0][k], x[i0][k]): three
+ * float roundings.  Where frac == 0 the kernel stores x[i0][k] itself and does not read x[i1], so c2 == c is the identity bit
+ * for bit (a negative zero and a non-finite neighbour included); a clip that is not to be warped is sent as that.  With
+ * warp != NULL every T_b must be <= 4096, so that num stays exact in float.
+ * Masks are applied to the warped frames, frequency first and then time; overlaps are harmless.  A cell (t, k) with t < T_b
+ * becomes mask_value if f0 <= k < f0 + f for any frequency mask or t0 <= t < t0 + w for any time mask.  The value is STORED,
+ * never multiplied in: a NaN or inf under a mask comes out as mask_value (the cell is not even read).  Masks are clamped into
+ * [0, 161) and [0, T_b): nothing outside the clip's frames is masked.
+ * Padding: frames t >= T_b are zero in out, whatever mask_value is.
+ * out == x (in place) is allowed only when warp == NULL: the kernel then stores the masked cells only and reads nothing (x's
+ * padding is what it was).  Otherwise out must not overlap x (refused), every cell of out is written, padding included, and
+ * out need not be initialised; warp == NULL with a separate out is a copy with masks.
+ * DS2_ERR_ARG before any launch: x, out or frames NULL; B outside 1..65535; t_max < 1; MF or MT outside 0..8; a NULL table with
+ * a non-zero count; x and out overlapping unless they are equal and warp == NULL.  All three tables NULL with MF == MT == 0 is
+ * not an error: in place the call returns at once, there is nothing to do.  frames and the tables are device data: the
+ * kernel clamps every entry (no entry can make it read or write outside the two buffers); a host wrapper validates them
+ * (T_b <= 4096 with a warp, c and c2 in range) before upload.
+ * No workspace, no atomics, no cell written twice: a clip's result does not depend on its position in the batch, on the other
+ * clips, on t_max, or on what out held before.
+ * Added without a change of DS2_ABI_VERSION: one new symbol, no existing signature altered. */
+int ds2_spec_augment(const float* x, float* out, int B, int t_max, const int32_t* frames, const int32_t* warp,
+                     const int32_t* fmask, int MF, const int32_t* tmask, int MT, float mask_value, void* stream);
+
 /* ------------------------------------------------------------------ generic fp32 GEMM (MFMA)
  * C[M,N] = op(A) * op(B) + beta * C, row-major with leading dimensions.  op(A)=A (M x K, lda) or
  * A^T (A stored K x M); op(B)=B (K x N, ldb) or B^T (B stored N x K).  beta is 0 or 1.
