@@ -79,7 +79,8 @@ __device__ __forceinline__ void load_slab(__amdgpu_buffer_rsrc_t rs, int ld, int
 
 // Fast path of load_slab for whole slabs: the per-lane byte offsets of a tile do not change from slab to slab, only a
 // wave-uniform advance does -- it goes into the buffer instruction's SCALAR offset.  Lanes outside the tile keep an
-// out-of-range vector offset (the range check ignores the scalar offset), so the loop body holds no address arithmetic:
+// out-of-range vector offset (OOB plus any slab's advance is still beyond every descriptor: the range check adds the scalar
+// offset to the vector offset, see split_load below, and the sum does not wrap), so the loop body holds no address arithmetic:
 // the general form above recomputes and re-checks every offset for every slab, ~80 vector instructions in front of each
 // slab's first MFMA.  Valid when every 16-byte chunk is wholly inside or outside the tile (VEC and xmax % 4 == 0 for the
 // x-contiguous form) and the slab does not cross kmax.
@@ -461,6 +462,12 @@ constexpr int SPLIT_TILE_BYTES = 128 * SP;      // one operand slab
 // slab loop holds no vector address arithmetic.  k beyond the operand: an x-contiguous source runs off the end of the
 // descriptor (k * ld + x >= (K - 1) * ld + xmax) and reads 0 by itself; a k-contiguous one would read its next row, so
 // the launcher only selects these kernels for it when K is a multiple of the slab depth.
+// The first half of that rests on the hardware: on gfx950 the descriptor's range check covers the k advance although it
+// rides in the SCALAR offset (vector offset + scalar offset is what is compared with the descriptor's size).
+// tests/test_gemm_edges_gpu.py shows it: TN products with K = 17, 40, 100, 333, 1000, 1283 in these kernels, A and B carved
+// out of NaN-filled storage with NaN pad columns and 48 ld + 64 NaN floats behind the last row, are exact -- were the advance
+// outside the check, rows K .. 16 ceil(K / 16) - 1 of both operands would be NaN and so would all of C.  The same check
+// keeps the prefetch of the two slabs behind the last one inside the operand's own span: nothing behind it is fetched.
 template <bool KCONTIG>
 __device__ __forceinline__ void split_voffsets(int ld, int x0, int xmax, int tid, int (&voff)[2]) {
     if (KCONTIG) {
