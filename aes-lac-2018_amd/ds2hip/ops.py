@@ -185,6 +185,42 @@ def noise_mix(wav, offsets, bank, noise_lo, noise_len, noise_start, levels, nois
     return (out, coef) if return_coef else out
 
 
+VAD_BLOCK = 160                         # DS2_VAD_BLOCK of include/ds2hip.h: samples per block of ds2_vad_segment (10 ms)
+VAD_BINS = 192                          # DS2_VAD_BINS: level bins
+
+
+def vad_segment(pcm, rank, margin_bins, min_bin, max_bin, min_speech, min_silence, pad, max_len, seg_cap=None, ws=None):
+    """Speech segments of one recording on the current stream (``ds2_vad_segment``; the rule is in include/ds2hip.h).
+    pcm: 1-D int16 on the device, at 16 kHz (a slice of a larger tensor is fine).  The other arguments are in blocks of 160
+    samples and level bins.  Returns ``(segs, info)``: segs (n_seg, 2) int32 on the HOST, rows [start_block, end_block) in
+    ascending order, and info = {n_seg, floor_bin, thr, speech_blocks, nb}; one readback brings both.  ``seg_cap``: rows
+    to provide (default: the rule's bound nb // min(min_speech, h) + 1); more segments than that raise.  ``ws``: a caller's
+    uint8 workspace of at least ``ds2_vad_segment_ws_bytes`` bytes (its contents do not matter); allocated here when None."""
+    if not isinstance(pcm, torch.Tensor) or not pcm.is_cuda or pcm.dtype != torch.int16 or pcm.dim() != 1:
+        raise RuntimeError('vad_segment takes a 1-D int16 tensor on the device')
+    if not pcm.is_contiguous():
+        raise RuntimeError('ds2hip entry points take contiguous tensors')
+    n = int(pcm.numel())
+    nb = (n + VAD_BLOCK - 1) // VAD_BLOCK
+    if seg_cap is None:
+        seg_cap = nb // max(min(int(min_speech), (int(max_len) + 1) // 2), 1) + 1
+    seg_cap = int(seg_cap)
+    ws_bytes = lib.query('ds2_vad_segment_ws_bytes', n)
+    if ws is None:
+        ws = torch.empty((int(ws_bytes),), dtype=torch.uint8, device=pcm.device)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < ws_bytes:
+        raise ValueError('vad_segment: the workspace must be uint8 on the device, of at least %d bytes' % ws_bytes)
+    out = torch.empty((8 + 2 * max(seg_cap, 0),), dtype=torch.int32, device=pcm.device)      # info, then the rows
+    lib.call('ds2_vad_segment', pcm.data_ptr() if n else None, n, int(rank), int(margin_bins), int(min_bin), int(max_bin),
+             int(min_speech), int(min_silence), int(pad), int(max_len), ws, ws.numel(), out[8:], seg_cap, out[:8])
+    host = out.cpu()
+    n_seg = int(host[0])
+    if n_seg > seg_cap:
+        raise RuntimeError('vad_segment: %d segments do not fit seg_cap = %d' % (n_seg, seg_cap))
+    info = dict(zip(('n_seg', 'floor_bin', 'thr', 'speech_blocks', 'nb'), host[:5].tolist()))
+    return host[8:].view(-1, 2)[:n_seg].clone(), info
+
+
 SPEC_MAX_MASKS = 8                      # masks of one kind per clip ds2_spec_augment takes
 SPEC_MAX_WARP_FRAMES = 4096             # with a warp: frame products stay exact in float (include/ds2hip.h)
 

@@ -418,6 +418,46 @@ int ds2_ctc_align(const float* probs, const int32_t* sizes, const int32_t* label
                   const int32_t* label_lens, int B, int T, int A, int max_label_len, int blank, int log_input, void* ws,
                   size_t ws_bytes, int32_t* states, int32_t* starts, int32_t* ends, float* score, void* stream);
 
+/* ------------------------------------------------------------------ voice-activity segmentation (csrc/vad.hip)
+ * Not in the reference (it cuts its corpora with dataset scripts and sox).  Cuts a recording of any length into the clips the
+ * model was trained on, from the int16 samples already on the device.  Integer arithmetic only: a result is exact.
+ * pcm: n int16 samples at 16 kHz.  A block is 160 samples (10 ms); nb = ceil(n / 160); block j covers samples
+ * [160 j, 160 j + 160), the part at or past n counting as zeros.
+ *   1. energies    E[j] = sum of x^2 over block j (64 bits, at most 160 * 2^30);  S[j] = E[j-1] + E[j] + E[j+1], missing
+ *                  neighbours counting as 0
+ *   2. level bin   bin(S) = S for S < 4; otherwise e = floor(log2 S), bin = 4 e + ((S >> (e - 2)) & 3): quarter-octave steps
+ *                  (0.58 .. 0.97 dB), monotone; the largest value is bin(3 * 160 * 2^30) = 155 (DS2_VAD_BINS = 192 bins)
+ *   3. threshold   hist = histogram of bin(S[j]) over the recording; floor_bin = the smallest k with hist[0] + .. + hist[k] >
+ *                  rank;  thr = min(max(floor_bin + margin_bins, min_bin), max_bin);  raw mask m[j] = bin(S[j]) >= thr
+ *                  (max_bin is what lets a recording that is speech throughout still count as speech)
+ *   4. close gaps  a maximal run of m = 0 shorter than min_silence blocks with speech on both sides becomes speech; leading
+ *                  and trailing silence is never bridged
+ *   5. drop blips  on the result of 4, a maximal run of m = 1 shorter than min_speech blocks is removed; 4 is not repeated
+ *   6. pad         each remaining run [s, e) becomes [max(0, s - pad), min(nb, e + pad)); 2 pad < min_silence, so padded runs
+ *                  never touch
+ *   7. split       with h = (max_len + 1) / 2: while e - s > max_len, cut at the c in [s + h, min(s + max_len, e - h)] with
+ *                  the smallest S[c] (ties: the smallest c), emit [s, c) and go on with s = c; then emit [s, e).  Every piece
+ *                  of a split run has between h and max_len blocks
+ *   8. output      the segments in ascending order as [start_block, end_block); at most nb / min(min_speech, h) + 1 of them.
+ *                  In samples a segment is [160 start, min(n, 160 end))
+ * segs (seg_cap, 2) int32: rows 0 .. min(n_seg, seg_cap) - 1 hold the segments, rows from n_seg up to seg_cap are -1; with
+ * n_seg > seg_cap only seg_cap rows are written, nothing past them is touched, and info[0] still holds the true count.
+ * info int32[8]: n_seg, floor_bin, thr, the number of speech blocks after step 5, nb, 0, 0, 0.  n = 0: no segment, info all 0.
+ * DS2_ERR_ARG before any launch: min_speech < 2; max_len < 4; pad < 0; 2 pad >= min_silence; rank outside 0 .. max(nb - 1, 0);
+ * margin_bins, min_bin or max_bin outside 0 .. 191; n >= 2^31; ws_bytes < ds2_vad_segment_ws_bytes(n); seg_cap < 1; a NULL or
+ * misaligned pointer (pcm: 2 bytes, any offset inside a tensor; ws: 16; segs, info: 4).
+ * Nothing outside pcm[0 .. n) is read.  ws and segs need not be zeroed; the result does not depend on what they held and is
+ * bit-identical from run to run (the only atomics are integer adds into the histogram).  Three launches on the stream: block
+ * energies (the one pass over the samples, 16 bytes per lane), S / bin / histogram, then steps 3-8 as scans over run
+ * boundaries in one workgroup.  No workgroup waits on another.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_VAD_BLOCK 160
+#define DS2_VAD_BINS 192
+size_t ds2_vad_segment_ws_bytes(size_t n);
+int ds2_vad_segment(const int16_t* pcm, size_t n, int rank, int margin_bins, int min_bin, int max_bin, int min_speech,
+                    int min_silence, int pad, int max_len, void* ws, size_t ws_bytes, int32_t* segs, int seg_cap,
+                    int32_t* info, void* stream);
+
 /* ------------------------------------------------------------------ CTC
  * Replaces warpctc_pytorch.CTCLoss (train.py:179, codes/engine.py:22, codes/metrics.py:51):
  * softmax over A inside, blank 0, costs[b] = -log p(labels_b | acts[:act_lens[b], b]),
