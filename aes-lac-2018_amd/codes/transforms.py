@@ -58,11 +58,12 @@ class BatchSpectrogram(object):
     clip's frames, percentage = T_i / float(T_max) stored as float32.
     """
 
-    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None, spec_augment=None):
+    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None, spec_augment=None, reverb=None):
         self.normalize, self.eps, self.device = normalize, eps, device
         self.scale = ops.amplitude_scale(scale)      # int16 clips (RawAudioBatch) come out as q * scale: see ToTensor
         self.noise = noise                           # a NoiseInjection: the bank the drawn noise of a batch is mixed from
         self.spec_augment = spec_augment             # a SpecAugment: resolves and applies the draws a batch carries
+        self.reverb = reverb                         # a Reverb: the bank the drawn impulse responses of a batch come from
 
     def __call__(self, wavs, offsets=None):
         spec = None
@@ -70,6 +71,9 @@ class BatchSpectrogram(object):
             if wavs.noise is not None and self.noise is None:
                 raise RuntimeError('the batch carries noise draws (ToTensor(noise=...)) but this BatchSpectrogram was '
                                    'built without a noise bank: pass noise=<the NoiseInjection> to it')
+            if wavs.reverb is not None and self.reverb is None:
+                raise RuntimeError('the batch carries reverberation draws (ToTensor(reverb=...)) but this BatchSpectrogram '
+                                   'was built without an RIR bank: pass reverb=<the Reverb> to it')
             spec = wavs.spec
             if spec is not None and self.spec_augment is None:
                 raise RuntimeError('the batch carries SpecAugment draws (ToTensor(spec_augment=...)) but this '
@@ -79,6 +83,8 @@ class BatchSpectrogram(object):
                 wavs.pcm.record_stream(torch.cuda.current_stream())
             pcm = wavs.pcm if wavs.pcm.is_cuda else wavs.pcm.to(self.device, non_blocking=True)
             flat, offs = ops.decode_augment(pcm, wavs.offsets, wavs.tempos, wavs.gains_db, scale=self.scale)
+            if wavs.reverb is not None:              # RIRs drawn by the loader: convolved between gain and noise
+                flat = self.reverb.apply_batch(flat, offs, wavs.reverb)
             if wavs.noise is not None:               # noise drawn by the loader: mixed in place, between gain and the STFT
                 self.noise.mix_batch(flat, offs, wavs.noise, self.scale)
             lens = [offs[i + 1] - offs[i] for i in range(len(offs) - 1)]
@@ -120,13 +126,15 @@ class Compose(object):
 class PCMClip(object):
     """What a loader worker hands on for one utterance: the int16 samples as read from the file plus the augmentation
     DRAWN for it (tempo factor, gain in dB; None = no augmentation; ``noise``: what ``NoiseInjection.draw`` returned;
-    ``spec``: what ``SpecAugment.draw`` returned).  The arithmetic -- int16 -> float, WSOLA tempo, gain, 16-bit
-    requantisation, noise mixing, and behind the spectrogram the SpecAugment masks -- happens on the GPU after collate
-    (``ds2hip.ops.decode_augment``, ``ds2hip.ops.noise_mix``, ``ds2hip.ops.spec_augment``)."""
-    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise', 'spec')
+    ``spec``: what ``SpecAugment.draw`` returned; ``reverb``: what ``Reverb.draw`` returned).  The arithmetic -- int16 ->
+    float, WSOLA tempo, gain, 16-bit requantisation, reverberation, noise mixing, and behind the spectrogram the SpecAugment
+    masks -- happens on the GPU after collate (``ds2hip.ops.decode_augment``, ``ds2hip.ops.reverb``,
+    ``ds2hip.ops.noise_mix``, ``ds2hip.ops.spec_augment``)."""
+    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise', 'spec', 'reverb')
 
-    def __init__(self, pcm, tempo=None, gain_db=None, noise=None, spec=None):
+    def __init__(self, pcm, tempo=None, gain_db=None, noise=None, spec=None, reverb=None):
         self.pcm, self.tempo, self.gain_db, self.noise, self.spec = pcm, tempo, gain_db, noise, spec
+        self.reverb = reverb
 
     def numel(self):
         return int(self.pcm.numel())
@@ -136,11 +144,11 @@ class RawAudioBatch(object):
     """A collated minibatch of ``PCMClip``s: ONE int16 buffer (page-locked when the DataLoader pins) + clip offsets +
     the per-clip augmentation parameters.  2 bytes per sample cross PCIe; everything else happens on the device.
     ``noise``: the clips' ``NoiseInjection.draw`` results (None for a clip without noise), or None when no clip drew any;
-    ``spec``: the same for ``SpecAugment.draw``."""
+    ``spec``: the same for ``SpecAugment.draw``; ``reverb``: the same for ``Reverb.draw``."""
 
-    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None, spec=None):
+    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None, spec=None, reverb=None):
         self.pcm, self.offsets, self.tempos, self.gains_db, self.noise = pcm, list(offsets), tempos, gains_db, noise
-        self.spec = spec
+        self.spec, self.reverb = spec, reverb
         self.ready = None                            # event recorded behind an asynchronous upload (DevicePrefetcher)
 
     @classmethod
@@ -154,7 +162,8 @@ class RawAudioBatch(object):
         gains = [0.0 if c.gain_db is None else float(c.gain_db) for c in clips] if aug else None
         noise = [c.noise for c in clips] if any(c.noise is not None for c in clips) else None
         spec = [c.spec for c in clips] if any(c.spec is not None for c in clips) else None
-        return cls(pcm, offs, tempos, gains, noise, spec)
+        reverb = [c.reverb for c in clips] if any(c.reverb is not None for c in clips) else None
+        return cls(pcm, offs, tempos, gains, noise, spec, reverb)
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -165,7 +174,7 @@ class RawAudioBatch(object):
 
     def to(self, device, non_blocking=False):
         out = RawAudioBatch(self.pcm.to(device, non_blocking=non_blocking), self.offsets, self.tempos, self.gains_db,
-                            self.noise, self.spec)
+                            self.noise, self.spec, self.reverb)
         return out
 
 
@@ -182,7 +191,9 @@ class ToTensor(object):
     without noise keeps its tempo / gain sequence -- and the clip's noise is mixed by the same device stage.
     ``spec_augment`` (a ``SpecAugment``, default None) adds ITS draw behind the noise draw, under the same rule, and the clip
     carries it to the ``BatchSpectrogram``: it needs ``defer=True`` (a waveform cannot carry a draw; in a per-clip pipeline
-    the object itself stands behind ``ToSpectrogram``, where ``get_default_transforms`` puts it).  There is no
+    the object itself stands behind ``ToSpectrogram``, where ``get_default_transforms`` puts it).  ``reverb`` (a ``Reverb``,
+    default None) adds its draw BETWEEN the gain draw and the noise draw, under the same rule -- the order of the stages on
+    the device: tempo, gain, reverberation, noise, spectrogram, SpecAugment.  There is no
     host implementation in the product; ``oracle/audio.py`` specifies the arithmetic (sox itself is absent from the
     reference tree, so the tempo change is the published WSOLA algorithm with sox's defaults, not sox's samples).
 
@@ -197,11 +208,11 @@ class ToTensor(object):
     ``num_workers=0``."""
 
     def __init__(self, sample_rate=16000, augment=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), defer=False,
-                 device='cuda', scale=None, noise=None, spec_augment=None):
+                 device='cuda', scale=None, noise=None, spec_augment=None, reverb=None):
         self.sample_rate, self.augment = sample_rate, augment
         self.tempo_range, self.gain_range = tempo_range, gain_range
         self.defer, self.device = defer, device
-        self.noise = noise
+        self.noise, self.reverb = noise, reverb
         if spec_augment is not None and not defer:
             raise ValueError('ToTensor(spec_augment=...) needs defer=True: the draw travels with the clip to the '
                              'BatchSpectrogram; in a per-clip pipeline put the SpecAugment behind ToSpectrogram')
@@ -224,6 +235,8 @@ class ToTensor(object):
         if self.augment:
             clip.tempo = float(np.random.uniform(low=self.tempo_range[0], high=self.tempo_range[1]))
             clip.gain_db = float(np.random.uniform(low=self.gain_range[0], high=self.gain_range[1]))
+        if self.reverb is not None:
+            clip.reverb = self.reverb.draw()
         if self.noise is not None:
             clip.noise = self.noise.draw()
         if self.spec_augment is not None:
@@ -237,6 +250,8 @@ class ToTensor(object):
         batch = RawAudioBatch.from_clips([clip]).to(self.device)
         wav, offs = ops.decode_augment(batch.pcm, batch.offsets, batch.tempos, batch.gains_db, self.sample_rate,
                                        scale=self.scale)
+        if batch.reverb is not None:
+            wav = self.reverb.apply_batch(wav, offs, batch.reverb)
         if batch.noise is not None:
             self.noise.mix_batch(wav, offs, batch.noise, self.scale)
         return wav.cpu()
@@ -406,6 +421,174 @@ class NoiseInjection(object):
             sum(self.lengths) / float(self.sample_rate))
 
 
+def rir_from_pcm(pcm, max_taps):
+    """The bank rule for one file: int16 samples -> float32 taps.  In float64, s = int16 / 32768; p = the first index of
+    max |s|; h = s[p : p + max_taps] / s[p]; trailing zeros stripped; rounded to float32.  h[0] == 1 exactly.  An all-zero
+    (or empty) file has no peak: ValueError."""
+    import numpy as np
+    s = np.asarray(pcm, np.int16).astype(np.float64).reshape(-1) / 32768.0
+    if s.size == 0 or not np.any(s):
+        raise ValueError('holds no impulse: every sample is zero' if s.size else 'holds no samples')
+    p = int(np.argmax(np.abs(s)))
+    h = s[p:p + int(max_taps)] / s[p]
+    nz = np.flatnonzero(h)
+    return h[:int(nz[-1]) + 1].astype(np.float32)
+
+
+class Reverb(object):
+    """Reverberation: with probability ``prob`` a clip is convolved with a room impulse response (RIR) drawn from the files
+    under ``path``.  The reference has nothing of the kind, so every rule here is a decision (README "Reverberation"); nobody
+    has measured the defaults' effect on WER in this model.
+
+    * ``path`` is searched recursively for ``.wav`` files, in sorted order (a missing directory raises ``IOError``).  Every
+      file must be 16-bit mono PCM at ``sample_rate`` = 16000; any other file is REFUSED by name -- another rate, width or
+      channel count, an empty or all-zero file -- and so is an empty directory.  Nothing is resampled.
+    * per file (``rir_from_pcm``): the RIR starts at the file's largest |sample| and is divided by it, so ``h[0] == 1`` and the
+      direct path is not delayed; what precedes the peak is dropped; at most ``int(max_rir_seconds * 16000)`` taps are kept,
+      trailing zeros are stripped.  A set with more than ``max_bank_seconds`` of taps in total raises ``ValueError`` rather
+      than being truncated (the bank lives on the GPU, 4 bytes per tap).
+    * ``draw()`` -- what a loader worker calls -- returns None or the file index from, in this order,
+      ``np.random.binomial(1, prob)`` and then, only on a hit, ``np.random.choice(n_files)``.
+    * ``y[n] = sum_k h[k] x[n - k]`` in fp32: the clip keeps its length (the tail is cut), and the history before its first
+      sample is zero.  The output is scaled back to the clip's own energy (``ops.reverb``'s ``keep_level``: the noise stage
+      behind it sets its level relative to the clip's rms), and is returned as floats, not requantised to 16 bit.
+
+    The arithmetic is one device launch pair for a whole minibatch (``ds2hip.ops.reverb``): the RIRs live on the GPU as one
+    float32 bank, built and uploaded on first use in the process that owns the GPU (never in a loader worker: the workers
+    only draw).  ``ToTensor(reverb=...)`` attaches the draw to its clip and ``BatchSpectrogram(reverb=...)`` convolves after
+    decode, tempo and gain, before the noise.  ``__call__(x)`` is the per-clip contract through the same kernel (a CPU
+    tensor makes a GPU round trip)."""
+
+    def __init__(self, path, sample_rate=16000, prob=0.3, max_rir_seconds=0.5, max_bank_seconds=600, device='cuda'):
+        import os
+        import threading
+        import wave
+        if path is None or not os.path.isdir(path):
+            raise IOError('Directory does not exist: {}'.format(path))
+        if int(sample_rate) != 16000:
+            raise ValueError('Reverb works at 16000 Hz only (nothing is resampled here), got sample_rate = %r' % (sample_rate,))
+        if not 0.0 <= float(prob) <= 1.0:
+            raise ValueError('Reverb: prob must lie in [0, 1], got %r' % (prob,))
+        self.path, self.sample_rate, self.prob = path, int(sample_rate), float(prob)
+        self.max_rir_seconds, self.max_bank_seconds = max_rir_seconds, max_bank_seconds
+        self.device = device
+        self.max_taps = int(max_rir_seconds * self.sample_rate)
+        if not 1 <= self.max_taps <= ops.REVERB_MAX_TAPS:
+            raise ValueError('Reverb: max_rir_seconds = %r is %d taps; the kernel takes 1..%d'
+                             % (max_rir_seconds, self.max_taps, ops.REVERB_MAX_TAPS))
+        self.paths = sorted(os.path.join(d, f) for d, _, files in os.walk(path) for f in files
+                            if f.lower().endswith('.wav'))
+        if not self.paths:
+            raise ValueError('no .wav file under the RIR directory {}'.format(path))
+        # headers first (every refusal names its file), then the bank rule once per file: where the peak stands and where
+        # the trailing zeros begin decide a file's tap count, which the size limit and ``params`` need, and an all-zero file
+        # is refused here, before training starts, not at the first batch.  The taps are not kept: the bank is built on
+        # first use in the process that owns the GPU
+        self.lengths = []
+        for p in self.paths:
+            try:
+                with wave.open(p, 'rb') as w:
+                    rate, width, chans, frames = w.getframerate(), w.getsampwidth(), w.getnchannels(), w.getnframes()
+            except (wave.Error, EOFError) as e:
+                raise ValueError('RIR file {} is not a PCM WAV file: {}'.format(p, e))
+            if rate != self.sample_rate or width != 2 or chans != 1:
+                raise ValueError('RIR file {}: {} Hz, {} bit, {} channel(s); the RIR bank takes 16-bit mono PCM at {} Hz '
+                                 'only (nothing is resampled here: convert the file)'.format(p, rate, 8 * width, chans,
+                                                                                            self.sample_rate))
+            if frames <= 0:
+                raise ValueError('RIR file {} holds no samples'.format(p))
+            self.lengths.append(int(self._taps(p).size))
+        total = sum(self.lengths)
+        if total > max_bank_seconds * self.sample_rate:
+            raise ValueError('the RIR files under {} hold {:.1f} s of taps, more than max_bank_seconds = {} (the bank lives '
+                             'on the GPU, 4 bytes per tap; nothing is truncated: raise the limit or thin the set)'.format(
+                                 path, total / float(self.sample_rate), max_bank_seconds))
+        self.starts = [0]
+        for n in self.lengths[:-1]:
+            self.starts.append(self.starts[-1] + n)
+        self._banks, self._lock = {}, threading.Lock()
+
+    def _taps(self, p):
+        import wave
+
+        import numpy as np
+        with wave.open(p, 'rb') as w:
+            pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+        try:
+            return rir_from_pcm(pcm, self.max_taps)
+        except ValueError as e:
+            raise ValueError('RIR file {} {}'.format(p, e))
+
+    def __getstate__(self):                          # (a spawned loader worker gets the description, never the device bank)
+        state = dict(self.__dict__)
+        state['_banks'], state['_lock'] = {}, None
+        return state
+
+    def __setstate__(self, state):
+        import threading
+        self.__dict__.update(state)
+        self._lock = threading.Lock()
+
+    def draw(self, rng=None):
+        """None (this clip stays dry) or the file index.  ``rng`` (a ``numpy.random.RandomState`` or ``Generator``)
+        replaces the global ``np.random`` when given."""
+        import numpy as np
+        r = np.random if rng is None else rng
+        if not r.binomial(1, self.prob):
+            return None
+        return int(r.choice(len(self.paths)))
+
+    def bank(self, device=None):
+        """The float32 taps of every file, concatenated in listing order, on ``device``: built and uploaded on first use."""
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('the RIR bank lives on the GPU and cannot be used in a DataLoader worker process; let the '
+                               'worker draw (ToTensor(reverb=..., defer=True)) and convolve after collate '
+                               '(BatchSpectrogram(reverb=...))')
+        import numpy as np
+        device = torch.device(self.device if device is None else device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        with self._lock:
+            bank = self._banks.get(device)
+            if bank is None:
+                parts = [self._taps(p) for p in self.paths]
+                for p, part, n in zip(self.paths, parts, self.lengths):
+                    if part.size != n:
+                        raise ValueError('RIR file {} gives {} taps, it gave {} at construction'.format(p, part.size, n))
+                bank = self._banks[device] = torch.from_numpy(np.concatenate(parts)).to(device)
+        return bank
+
+    def params(self, draws):
+        """Per-clip (rir_lo, rir_len) for ``ops.reverb`` from the clips' draws."""
+        lo, ln = [], []
+        for d in draws:
+            lo.append(0 if d is None else self.starts[d]), ln.append(0 if d is None else self.lengths[d])
+        return lo, ln
+
+    def apply_batch(self, flat, offsets, draws, return_gain=False):
+        """Convolve the drawn clips of the flat float buffer, one launch pair on the current stream.  Returns the NEW flat
+        buffer (the convolution is out of place; undrawn clips are copied)."""
+        lo, ln = self.params(draws)
+        return ops.reverb(flat, offsets, self.bank(flat.device), lo, ln, True, return_gain=return_gain)
+
+    def __call__(self, x):
+        """x: 1-D float tensor of samples -> the same clip, reverberated with probability ``prob``, on x's device."""
+        assert isinstance(x, torch.Tensor) and x.dim() == 1, 'Only mono audio is accepted'
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('Reverb convolves on the GPU and cannot run in a DataLoader worker process; let the worker '
+                               'draw (ToTensor(reverb=..., defer=True)) and convolve after collate, or use num_workers=0')
+        draw = self.draw()
+        if draw is None or x.numel() == 0:
+            return x
+        wav = x.to(self.device, torch.float32).contiguous()
+        return self.apply_batch(wav, [0, wav.numel()], [draw]).to(x.device)
+
+    def __repr__(self):
+        return '{}({}, sample_rate={}, prob={}, max_rir_seconds={}, files={}, taps={})'.format(
+            self.__class__.__name__, self.path, self.sample_rate, self.prob, self.max_rir_seconds, len(self.paths),
+            sum(self.lengths))
+
+
 class SpecAugment(object):
     """SpecAugment (Park et al. 2019) on the log-spectrogram: a time warp, ``freq_masks`` frequency masks and ``time_masks``
     time masks per clip.  The reference has nothing of the kind -- its augmentation is tempo, gain and noise, all on the
@@ -527,6 +710,15 @@ def waveform_spec_augment(transform):
     for t in getattr(transform, 'transforms', [transform]):
         if isinstance(t, ToTensor):
             return t.spec_augment
+    return None
+
+
+def waveform_reverb(transform):
+    """The ``Reverb`` whose draws the ``ToTensor`` stage of ``transform`` attaches to its clips (None when there is none):
+    what the ``BatchSpectrogram`` that decodes those clips must be built with."""
+    for t in getattr(transform, 'transforms', [transform]):
+        if isinstance(t, ToTensor):
+            return t.reverb
     return None
 
 

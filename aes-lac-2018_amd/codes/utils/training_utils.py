@@ -3,7 +3,7 @@
 Config schema (unchanged): ``model{name, langs, freeze_layers, map_fc, params}``,
 ``training{num_epochs, batch_size, max_norm, augment, finetune}``, ``optimizer{name, params, per_layer_lr}``,
 ``scheduler{name, params}``.  Additions: ``training.audio_scale`` (``audio_scale``) and the optional block
-``training.noise{path, noise_levels, prob}`` (``get_noise``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
+``training.noise{path, noise_levels, prob}`` (``get_noise``), ``training.reverb{path, prob, ...}`` (``get_reverb``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
 (SURVEY.md section 4): ``langs[0]`` is the fine-tune target language, the new FC layer's *weight* is
 normally initialised.
 """
@@ -31,7 +31,10 @@ def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     ``training.spec_augment`` (``get_spec_augment``) travels the same way: the training ``ToTensor`` draws
     (``transforms.waveform_spec_augment(train_t)`` is what the training ``BatchSpectrogram`` is built with), or, without
     ``gpu_frontend``, the ``SpecAugment`` stands behind the spectrogram.
-    ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at either block."""
+    ``training.reverb`` (``get_reverb``) likewise: the training ``ToTensor`` draws (``transforms.waveform_reverb(train_t)``
+    is what the training ``BatchSpectrogram`` is built with), or, without ``gpu_frontend``, the ``Reverb`` stands in front
+    of the ``NoiseInjection``.
+    ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at any of these blocks."""
     augment = bool(config.training.get('augment', False))       # tempo + gain on the training set only
     # gpu_frontend: workers hand on int16 clips + the drawn (tempo, gain); decode, WSOLA, gain and the spectrogram all run
     # on the device after collate.  Otherwise the reference's per-utterance contract (each transform returns a tensor).
@@ -39,12 +42,13 @@ def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     scale = audio_scale(config)
     bank = get_noise(data_dir, config, scale) if noise else None
     spec = get_spec_augment(config) if noise else None
+    rir = get_reverb(data_dir, config) if noise else None
     if gpu_frontend:
         train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=True, scale=scale, noise=bank,
-                                                          spec_augment=spec)])
+                                                          spec_augment=spec, reverb=rir)])
     else:
         train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=False, scale=scale)] +
-                                     ([bank] if bank is not None else []) + tail + ([spec] if spec is not None else []))
+                                     ([rir] if rir is not None else []) + ([bank] if bank is not None else []) + tail + ([spec] if spec is not None else []))
     val_t = transforms.Compose([transforms.ToTensor(augment=False, defer=gpu_frontend, scale=scale)] + tail)
     target_t = [transforms.ToLabel(os.path.join(data_dir, 'labels.{}.json'.format(lang)), lang=lang,
                                    remove_accents=(lang != 'pt_BR')) for lang in config.model.langs]
@@ -73,6 +77,29 @@ def get_noise(data_dir, config, scale=None):
         raise ValueError('training.noise takes path (required), noise_levels, prob, max_bank_seconds; got %s' % sorted(block))
     kwargs = {k: block[k] for k in ('noise_levels', 'prob', 'max_bank_seconds') if k in block}
     return transforms.NoiseInjection(_resolve(block['path'], data_dir), scale=scale, **kwargs)
+
+
+REVERB_KEYS = ('path', 'prob', 'max_rir_seconds', 'max_bank_seconds')
+
+
+def get_reverb(data_dir, config):
+    """``training.reverb`` of the JSON config (an addition to the reference's schema): ``{"path": DIR, "prob": p,
+    "max_rir_seconds": s, "max_bank_seconds": S}`` -> a ``transforms.Reverb`` (None without the block).  ``path`` is required;
+    keys left out keep the constructor's defaults; an unknown key is refused by name.  Independent of ``training.augment``,
+    ``training.noise`` and ``training.spec_augment``; a relative ``path`` that does not exist from the working directory is
+    looked up under ``--data-dir``.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""
+    training = config.get('training', {}) if hasattr(config, 'get') else {}
+    block = (training or {}).get('reverb', None)
+    if not block:
+        return None
+    unknown = sorted(set(block) - set(REVERB_KEYS))
+    if unknown:
+        raise ValueError('training.reverb: unknown key(s) %s; it takes %s' % (', '.join(unknown), ', '.join(REVERB_KEYS)))
+    if 'path' not in block:
+        raise ValueError('training.reverb needs path (the directory of RIR files); got %s' % sorted(block))
+    rir = transforms.Reverb(_resolve(block['path'], data_dir), **{k: block[k] for k in REVERB_KEYS[1:] if k in block})
+    LOG.info('Reverberation on the training set: {}'.format(rir))
+    return rir
 
 
 SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'time_warp', 'prob', 'mask_value')

@@ -185,6 +185,61 @@ def noise_mix(wav, offsets, bank, noise_lo, noise_len, noise_start, levels, nois
     return (out, coef) if return_coef else out
 
 
+REVERB_TILE = 2048                      # DS2_REVERB_TILE of include/ds2hip.h: outputs of one clip per workgroup of ds2_reverb
+REVERB_TAPS_STEP = 512                  # DS2_REVERB_TAPS_STEP: taps staged per pass
+REVERB_MAX_TAPS = 65536                 # DS2_REVERB_MAX_TAPS: taps of one RIR
+
+
+def reverb(wav, offsets, bank, rir_lo, rir_len, keep_level=True, out=None, return_gain=False, ws=None):
+    """Reverberation for a minibatch in one launch pair on the current stream (``ds2_reverb``): every drawn clip is convolved
+    with its room impulse response, keeps its length and (``keep_level``) its energy.
+    wav: the flat float clips ``decode_augment`` returns, offsets: its python list (B+1).  bank: every RIR's float32 taps
+    concatenated on the device; per clip (python sequences of length B) ``rir_lo`` / ``rir_len`` the RIR (length 0 = no
+    draw: the clip is copied bit for bit).  Returns the new flat buffer (``out``, never ``wav`` itself; a new tensor when
+    None, with the samples outside every clip copied from ``wav``), and the per-clip gains (B,) float32 on the device with
+    ``return_gain``.  ``ws``: a caller's uint8 workspace of at least ``ds2_reverb_ws_bytes`` bytes (its contents do not
+    matter); allocated here when None."""
+    import numpy as np
+    bsz = len(offsets) - 1
+    if not (isinstance(wav, torch.Tensor) and isinstance(bank, torch.Tensor) and wav.is_cuda and bank.is_cuda) or \
+            wav.dtype != torch.float32 or bank.dtype != torch.float32:
+        raise RuntimeError('reverb takes a float32 waveform buffer and a float32 RIR bank, both on the device')
+    off = np.asarray(offsets, np.int64)
+    lo, ln = (np.asarray(v, np.int64).reshape(-1) for v in (rir_lo, rir_len))
+    if not (len(lo) == len(ln) == bsz >= 1):
+        raise ValueError('reverb: one (rir_lo, rir_len) per clip, got %d / %d for %d clips' % (len(lo), len(ln), bsz))
+    if off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > wav.numel():
+        raise ValueError('reverb: offsets do not describe clips inside the waveform buffer')
+    drawn = ln > 0
+    if (ln < 0).any() or (lo[drawn] < 0).any() or (lo[drawn] + ln[drawn] > bank.numel()).any():
+        raise ValueError('reverb: an impulse response lies outside the bank (%d taps)' % bank.numel())
+    if (ln > REVERB_MAX_TAPS).any():
+        raise ValueError('reverb: an impulse response has %d taps, more than %d' % (int(ln.max()), REVERB_MAX_TAPS))
+    if out is None:
+        out = torch.empty_like(wav)
+        if off[0] > 0 or off[-1] < wav.numel():          # (samples outside every clip pass through)
+            out.copy_(wav)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and out.numel() >= int(off[-1])):
+        raise ValueError('reverb: out must be a contiguous float32 device tensor that holds every clip')
+    else:
+        a0, a1 = wav.data_ptr(), wav.data_ptr() + 4 * wav.numel()
+        b0, b1 = out.data_ptr(), out.data_ptr() + 4 * out.numel()
+        if a0 < b1 and b0 < a1:
+            raise ValueError('reverb: out overlaps wav; the convolution is out of place (every output reads K inputs)')
+    meta_d = upload_small(torch.from_numpy(np.concatenate([off, lo, ln])), wav.device)      # one upload
+    a = bsz + 1
+    ws_bytes = lib.query('ds2_reverb_ws_bytes', bsz, int(np.diff(off).max()))
+    if ws is None:
+        ws = torch.empty((int(ws_bytes),), dtype=torch.uint8, device=wav.device)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < ws_bytes:
+        raise ValueError('reverb: the workspace must be uint8 on the device, of at least %d bytes' % ws_bytes)
+    gain = _empty((bsz,), wav) if return_gain else None
+    lib.call('ds2_reverb', wav, meta_d[:a], bsz, bank, meta_d[a:a + bsz], meta_d[a + bsz:], int(bool(keep_level)), out, gain,
+             ws, int(ws.numel()))
+    return (out, gain) if return_gain else out
+
+
 VAD_BLOCK = 160                         # DS2_VAD_BLOCK of include/ds2hip.h: samples per block of ds2_vad_segment (10 ms)
 VAD_BINS = 192                          # DS2_VAD_BINS: level bins
 

@@ -116,6 +116,44 @@ int ds2_noise_mix(const float* wav, const int64_t* offsets, int B, const int16_t
                   const int64_t* noise_len, const int64_t* noise_start, const float* level, float noise_scale, float* out,
                   float* coef, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ reverberation
+ * Convolution of every drawn clip of a minibatch with a room impulse response (RIR), between the gain stage and the noise
+ * stage above (tempo -> gain -> reverberation -> noise -> spectrogram -> SpecAugment).  The reference has no such stage:
+ * nothing here is parity, every rule is a decision.
+ *   wav, offsets   clip b = wav[offsets[b] .. offsets[b+1]), n_b samples: the float output of the decode above
+ *   bank           the float taps of every RIR, concatenated; clip b's RIR is h = bank[rir_lo[b] .. rir_lo[b] + rir_len[b]),
+ *                  K = rir_len[b] taps, at most DS2_REVERB_MAX_TAPS (clamped into [0, that]).  The bank rule (host,
+ *                  codes/transforms.py Reverb): per 16-bit mono 16 kHz file, in float64, s = int16 / 32768, p = the first
+ *                  index of max |s|, h = s[p : p + max_taps] / s[p], trailing zeros stripped, rounded to float32 -- so
+ *                  h[0] == 1 exactly, the direct path is not delayed and what precedes the peak is dropped.
+ *   rir_len[b]==0  no draw: out equals wav bit for bit there (-0.0 and NaN payloads included) and gain[b] = 1
+ * Convolution:  y[n] = sum_{k=0}^{min(n, K-1)} h[k] x[n-k]  for n in [0, n_b), in fp32: the clip keeps its length, the tail
+ * is cut, and the history before the clip's first sample is zero -- never the neighbouring clip.  Each y[n] is one chain of
+ * fused multiply-adds in ONE accumulator, from the last tap down to h[0] (v_mfma_f32_16x16x4_f32, exact fp32; zero products
+ * stand in the chain where the 16x16 tile reaches past the RIR).  Nothing outside the clip or outside the RIR is loaded, so
+ * a NaN next door never reaches a product; a NaN or infinity INSIDE the clip or its RIR may spread to outputs up to 31
+ * samples away from those the sum itself names (0 * NaN in those zero products).
+ * Level (keep_level = 1):  Ex = sum x[n]^2 and Ey = sum y[n]^2 in float64 over exact products, over x and over the kernel's
+ * own fp32 y, in a fixed order;  gain = (float)sqrt(Ex / Ey), and 1 when Ey == 0 or the quotient is not finite;
+ * out[n] = gain * y[n], ONE rounded fp32 multiply.  keep_level = 0: out = y, gain = 1.  Floats out, not requantised.
+ * out == wav is refused (every output reads K inputs); samples of out outside every clip are not written.  gain (B floats)
+ * may be NULL.  Two kernels: a workgroup convolves DS2_REVERB_TILE consecutive outputs of one clip (tiles counted from the
+ * clip's own start), staging taps and samples through LDS in passes of DS2_REVERB_TAPS_STEP taps, writes the unscaled y to
+ * out and ONE (Ex, Ey) pair to ws; then every workgroup sums its clip's pairs in index order and scales its tile in place.
+ * No atomics: a clip's output bits and its gain depend on the clip and its RIR only -- not on its position in the batch or
+ * in memory, the other clips, what ws held, or a ws larger than required.
+ * ws >= ds2_reverb_ws_bytes(B, longest clip) bytes, need not be zeroed; ws_bytes fixes the grid (ws_bytes / (16 B) tiles per
+ * clip; with less than required the workgroups of a longer clip take several tiles each, every sample is still produced,
+ * and the order of the energy sum follows the grid) and must hold at least one pair per clip.  B in 1..65535.
+ * DS2_REVERB_FORM=valu in the environment selects the plain vector-ALU form of the same sum (the timing baseline).
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_REVERB_TILE 2048
+#define DS2_REVERB_TAPS_STEP 512
+#define DS2_REVERB_MAX_TAPS 65536
+size_t ds2_reverb_ws_bytes(int B, size_t max_clip_len);
+int ds2_reverb(const float* wav, const int64_t* offsets, int B, const float* bank, const int64_t* rir_lo,
+               const int64_t* rir_len, int keep_level, float* out, float* gain, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ SpecAugment
  * Time warp, frequency masks and time masks on the log-spectrogram of a minibatch, one launch, between ds2_spectrogram_fwd and
  * the model.  The reference has no such stage (its augmentation is tempo, gain and noise, all on the waveform): nothing here is

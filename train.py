@@ -23,7 +23,8 @@ from codes.ctc import CTCLoss as warp_CTCLoss  # noqa: E402
 from codes.data import TaskCounts, split_tasks  # noqa: E402
 from codes.decoder import GreedyDecoder  # noqa: E402
 from codes.engine import create_evaluator, create_trainer  # noqa: E402
-from codes.transforms import BatchSpectrogram, waveform_noise, waveform_scale, waveform_spec_augment  # noqa: E402
+from codes.transforms import (BatchSpectrogram, waveform_noise, waveform_reverb, waveform_scale,  # noqa: E402
+                              waveform_spec_augment)
 from codes.utils import model_utils as mu  # noqa: E402
 from codes.utils import training_utils as tu  # noqa: E402
 from codes.utils.dist_utils import data_parallel_env  # noqa: E402
@@ -176,7 +177,7 @@ def main(argv=None):
     # (one frontend for both loaders, and for every task of a multi-task run: only training clips ever carry noise or
     # SpecAugment draws, so validation never touches the bank and is never masked)
     frontend = BatchSpectrogram(device=device, scale=waveform_scale(train_t), noise=waveform_noise(train_t),
-                                spec_augment=waveform_spec_augment(train_t))
+                                spec_augment=waveform_spec_augment(train_t), reverb=waveform_reverb(train_t))
     for ld in (train_loader, val_loader):            # decode + augmentation + STFT of the NEXT bin run on the prefetch stream
         if hasattr(ld, 'frontend'):
             ld.frontend = frontend
