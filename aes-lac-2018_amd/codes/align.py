@@ -3,10 +3,12 @@
 transcript as the constraint: ``ds2_ctc_align`` (``csrc/ctc_align.hip``) finds the best single alignment of every
 utterance of a minibatch in one launch, and the host part below turns its frames into characters, words and seconds.
 """
+import math
+
 import numpy as np
 import torch
 
-from ds2hip import ops
+from ds2hip import lib, ops
 
 from .preprocessing import OrderedLabelEncoder
 
@@ -83,3 +85,73 @@ class ForcedAligner(object):
             chars = self._chars(targets_n[o:o + n], starts[b, :n], ends[b, :n]) if np.isfinite(sc) else []
             out.append({'score': sc, 'score_per_frame': sc / max(frames, 1), 'chars': chars, 'words': group_words(chars)})
         return out
+
+
+def diagonal_band(T, S, W):
+    """The band that follows the diagonal of the (T, S) lattice: int64 ``lo[t] = min(max((t (S-1)) // max(T-1, 1) - W//2, 0),
+    max(S - W, 0))``.  Integers only and non-decreasing; it admits states 0 / 1 at the first frame and, from two frames on,
+    S - 1 at the last."""
+    T, S, W = int(T), int(S), int(W)
+    t = torch.arange(T, dtype=torch.int64)
+    lo = torch.div(t * (S - 1), max(T - 1, 1), rounding_mode='floor') - W // 2
+    return lo.clamp_(min=0).clamp_(max=max(S - W, 0))
+
+
+def band_margin(states, lo, W, S):
+    """The smallest distance of a state path to a band edge that actually restricts it: ``min(states - lo)`` over the frames
+    with ``lo > 0`` and ``min(lo + W - 1 - states)`` over the frames with ``lo + W < S``; None when no frame is restricted.
+    An indicator, not a proof: a free optimum that lies far outside the band leaves no trace in the banded path."""
+    states = torch.as_tensor(states).to(torch.int64).reshape(-1)
+    lo = torch.as_tensor(lo).to(states.device, torch.int64).reshape(-1)
+    below, above = states - lo, lo + int(W) - 1 - states
+    lower, upper = lo > 0, lo + int(W) < int(S)
+    found = []
+    if bool(lower.any()):
+        found.append(int(below[lower].min()))
+    if bool(upper.any()):
+        found.append(int(above[upper].min()))
+    return min(found) if found else None
+
+
+class LongAligner(ForcedAligner):
+    """Alignment of ONE long recording's probabilities to its whole transcript with ``ds2_ctc_align_banded`` on a diagonal
+    band.  ``align(probs (T,A) on the device, labels)`` starts at the smallest band the library takes that is at least
+    ``min(S, band_states)`` states wide (S = 2 L + 1) and doubles it while there is no alignment inside the band or the
+    path comes closer than ``band_margin`` states to a restricting edge, until the band holds all S states or is the
+    library's widest; the last attempt is returned as it is: ``score``, ``score_per_frame``, ``chars``, ``words`` (as
+    ``ForcedAligner``), ``states`` (int32 tensor (T,) on the device, -1 without an alignment), ``band_states`` (the width
+    used) and ``band_margin`` (``band_margin()`` of the path; None without an alignment or a restricting edge)."""
+
+    def __init__(self, label_encoder, band_states=4096, band_margin=16, blank_index=0, log_input=False):
+        super().__init__(label_encoder, blank_index, log_input)
+        self.band_states, self.band_margin = int(band_states), int(band_margin)
+        if self.band_states < 1:
+            raise ValueError('LongAligner: band_states = %r is not a positive number of states' % (band_states,))
+
+    def align(self, probs, labels):
+        if not probs.is_cuda:
+            raise RuntimeError('LongAligner.align runs on device tensors only')
+        if probs.dim() != 2:
+            raise ValueError('LongAligner.align takes the (T,A) probabilities of one recording')
+        dev, t_n = probs.device, int(probs.shape[0])
+        labels_h = torch.as_tensor(np.asarray(labels, dtype=np.int64).reshape(-1)).to(torch.int32)
+        n = int(labels_h.numel())
+        s_n = 2 * n + 1
+        i32 = lambda v: torch.tensor([v], dtype=torch.int32, device=dev)    # noqa: E731
+        p, labels_d = probs.detach().contiguous().float()[None], labels_h.to(dev)
+        width = max(lib.ALIGN_BAND_MIN, 1 << max(min(s_n, self.band_states) - 1, 0).bit_length())
+        width = min(width, lib.ALIGN_BAND_MAX)
+        while True:
+            lo = diagonal_band(t_n, s_n, width)
+            states, starts, ends, score = ops.ctc_align_banded(
+                p, i32(t_n), labels_d, i32(0), i32(n), n, lo.to(dev, torch.int32)[None], width, self.blank_index,
+                self.log_input)
+            sc = float(score[0])
+            margin = band_margin(states[0], lo, width, s_n) if math.isfinite(sc) and t_n else None
+            tight = not math.isfinite(sc) or (margin is not None and margin < self.band_margin)
+            if not tight or width >= s_n or width >= lib.ALIGN_BAND_MAX:
+                break
+            width *= 2
+        chars = self._chars(labels_h.numpy(), starts[0].cpu().numpy(), ends[0].cpu().numpy()) if math.isfinite(sc) else []
+        return {'score': sc, 'score_per_frame': sc / max(t_n, 1), 'chars': chars, 'words': group_words(chars),
+                'states': states[0], 'band_states': width, 'band_margin': margin}

@@ -1,0 +1,307 @@
+// Banded CTC forced alignment: ds2_ctc_align's max-sum recursion restricted to a moving band of W states per frame, so that
+// work and workspace are T x W instead of T x (2 L + 1) -- an hour of audio against its whole transcript in one launch.
+//
+// One workgroup per utterance, ONE launch, no workgroup waits on another.  Everything that ctc_align.hip says about the
+// recursion, its fp64 scores, the per-frame term and the tie rule holds here; what differs:
+//   band        at frame t the admissible states are lo[t] <= s < lo[t] + W (and s < S = 2 L + 1).  State s lives in SLOT
+//               s mod W of the score row and of the frame's W back-pointer bytes, so a band that slides moves no data: the
+//               slot of a state that leaves the band is taken over by the state W above it.  Thread tid owns the slots
+//               tid + NTHR k, k < K = W / NTHR (lane-contiguous, so the three LDS reads per state are conflict-free and the
+//               pointer bytes of a wave are one 64-byte run).  The state a slot holds follows from lo[t] alone:
+//               s = lo[t] + ((slot - lo[t]) mod W).
+//   predecessors s - d (d = 0, 1, 2) of frame t - 1 are read from slot (slot - d) mod W and count only if
+//               lo[t-1] <= s - d < lo[t-1] + W: otherwise that slot holds another state's score (or nothing) and the
+//               predecessor is -inf, as the definition (the full recursion with inadmissible cells forced to -inf) has it.
+//               Nothing needs resetting.  Frame 0 reads the virtual row {state 0: 0, rest -inf} with band [0, W).
+//   lo          staged through LDS with the emissions, a chunk of frames ahead; every thread reads the frame's value (a
+//               broadcast) and compares it with the previous frame's: lo < 0, a decrease, a step of W or more (two bands
+//               that share no state) or lo >= S (a band that admits no state) ends the recursion for the whole workgroup
+//               at once -- "no alignment".
+//   symbols     a thread keeps the symbol and the skip flag of each of its K states in registers and re-reads them from
+//               labels (L2-resident) only when the band's movement puts another state into that slot.
+//   score       float64: an hour's path score is about -1e5.
+// Score rows: 2 x W doubles of dynamic LDS (128 KiB at W = 8192; the static part is 17 KiB).  Back-trace as in ctc_align.hip.
+// Critical path: T barriers per utterance, then T dependent LDS reads of one thread.
+#include "ds2_common.h"
+
+namespace {
+
+constexpr int BAND_MIN = DS2_ALIGN_BAND_MIN, BAND_MAX = DS2_ALIGN_BAND_MAX;
+constexpr int EM_FLOATS = 1024;          // per staging buffer: CH = min(32, 1024 / A) frames
+constexpr int EM_NLD = 4;                // staging loads per thread and chunk (threads 0..255 do the staging)
+constexpr int MAX_CH = 32;
+constexpr int MAX_A = 256;               // CH >= 4
+constexpr int BT_F = 64;                 // back-trace: frames per window
+constexpr int BT_W = 2 * BT_F;           // ... and states per window row (the walk needs 2 (BT_F - 1) + 1)
+#define NEG_INF_D (-(double)INFINITY)
+
+template <int W, int NTHR, int K>
+__global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
+    const float* __restrict__ probs, const int32_t* __restrict__ sizes, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ label_lens, const int32_t* __restrict__ lo_all,
+    int T, int A, int lmax, int blank, int log_input, uint8_t* bp_all, int32_t* __restrict__ states,
+    int32_t* __restrict__ starts, int32_t* __restrict__ ends, double* __restrict__ score) {
+    static_assert(NTHR * K == W || (K == 1 && NTHR > W), "every slot has one owner");
+    extern __shared__ double rowbuf[];   // [2][W], slot = state mod W
+    __shared__ float em[2][EM_FLOATS];
+    __shared__ int lo_s[2][MAX_CH];
+    __shared__ uint8_t win[BT_F][BT_W];
+    __shared__ int path[BT_F + 2];       // path[1 + f] = state at frame t_lo + f; [0] / [n + 1] = the frames around the window
+    __shared__ int bad;
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Lraw = label_lens[b];
+    const bool len_ok = Lraw >= 0 && Lraw <= lmax;
+    const int L = len_ok ? Lraw : 0;
+    const int tl = min(max(sizes[b], 0), T);
+    const int S = 2 * L + 1;
+    if (tid == 0) bad = len_ok ? 0 : 1;
+    __syncthreads();
+    const int32_t* lab = labels + label_offsets[b];
+    for (int l = tid; l < L; l += NTHR) {
+        const int sym = lab[l];
+        if (sym < 0 || sym >= A || sym == blank) bad = 1;   // reported as infeasible, never used as an index
+    }
+    for (int i = tid; i < W; i += NTHR) {
+        rowbuf[i] = (i == 0) ? 0.0 : NEG_INF_D;             // the virtual row before frame 0
+        rowbuf[W + i] = NEG_INF_D;
+    }
+    __syncthreads();
+
+    int32_t* st_out = states + (size_t)b * T;
+    int32_t* start_out = starts + (size_t)b * lmax;
+    int32_t* end_out = ends + (size_t)b * lmax;
+    for (int t = tl + tid; t < T; t += NTHR) st_out[t] = -1;
+    for (int l = L + tid; l < lmax; l += NTHR) start_out[l] = end_out[l] = -1;
+
+    uint8_t* bp = bp_all + (size_t)b * T * W;
+    double final_v = NEG_INF_D;
+    int final_s = -1;
+    if (!bad && tl > 0) {
+        int held[K], symskip[K];                            // the state each owned slot holds; its symbol | skip << 8
+#pragma unroll
+        for (int k = 0; k < K; ++k) held[k] = -1, symskip[k] = 0;
+        // staging roles: thread tid < 256 carries elements idx = tid + 256 i of a chunk (CH frames of A floats, contiguous),
+        // thread tid < CH the chunk's lo[tid]
+        const int CH = min(MAX_CH, EM_FLOATS / A), nper = CH * A;
+        const int nchunk = (tl + CH - 1) / CH;
+        const float* pb = probs + (size_t)b * T * A;
+        const int32_t* lo_row = lo_all + (size_t)b * T;
+        float ra[EM_NLD];
+        int rlo = 0;
+        auto stage_load = [&](int c) {
+            const int left = (tl - c * CH) * A;             // floats of valid frames from this chunk's start on
+#pragma unroll
+            for (int i = 0; i < EM_NLD; ++i) {
+                const int idx = tid + 256 * i;
+                ra[i] = 0.f;
+                if (tid < 256 && idx < nper && idx < left) ra[i] = pb[(size_t)c * nper + idx];
+            }
+            rlo = 0;
+            if (tid < CH && c * CH + tid < tl) rlo = lo_row[c * CH + tid];
+        };
+        auto stage_store = [&](int buf) {
+#pragma unroll
+            for (int i = 0; i < EM_NLD; ++i) {
+                const int idx = tid + 256 * i;
+                if (tid < 256 && idx < nper) {
+                    float a = ra[i];
+                    asm volatile("" : "+v"(a));             // keeps the wait for the loads HERE, at the chunk's last frame
+                    if (!log_input) a = logf(a);            // log 0 = -inf, log of a negative = NaN
+                    em[buf][idx] = (a == a) ? a : -INFINITY;
+                }
+            }
+            if (tid < CH) lo_s[buf][tid] = rlo;
+        };
+        stage_load(0);
+        stage_store(0);
+        __syncthreads();
+        int cur = 0, t = 0, lo_prev = 0;
+        bool dead = false;
+        for (int c = 0; c < nchunk && !dead; ++c) {
+            const bool more = c + 1 < nchunk;
+            if (more) stage_load(c + 1);                    // in flight while this chunk's frames are worked on
+            const int fend = min(CH, tl - c * CH);
+            for (int f = 0; f < fend; ++f) {
+                const int lo_t = lo_s[c & 1][f];
+                if (lo_t < lo_prev || lo_t >= S || lo_t - lo_prev >= W) {   // the same value in every thread: all leave together
+                    dead = true;
+                    break;
+                }
+                const double* prev = rowbuf + cur * W;
+                double* nxt = rowbuf + (cur ^ 1) * W;
+                const float* e = em[c & 1] + f * A;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int j = tid + NTHR * k;
+                    const unsigned su = (unsigned)lo_t + (unsigned)((j - lo_t) & (W - 1));
+                    if ((NTHR <= W || j < W) && su < (unsigned)S) {
+                        const int s = (int)su;
+                        if (s != held[k]) {
+                            int sym = blank, skip = 0;
+                            if (s & 1) {
+                                sym = lab[s >> 1];
+                                skip = s >= 3 && sym != lab[(s >> 1) - 1];
+                            }
+                            held[k] = s;
+                            symskip[k] = sym | (skip << 8);
+                        }
+                        const int d = s - lo_prev;          // >= 0; the predecessor s - i is in frame t-1's band iff d - i is in 0..W-1
+                        const double r0 = prev[j], r1 = prev[(j - 1) & (W - 1)], r2 = prev[(j - 2) & (W - 1)];
+                        const float ev = e[symskip[k] & 255];
+                        const double x0 = (unsigned)d < (unsigned)W ? r0 : NEG_INF_D;
+                        const double x1 = (unsigned)(d - 1) < (unsigned)W ? r1 : NEG_INF_D;
+                        const double x2 = ((symskip[k] >> 8) && (unsigned)(d - 2) < (unsigned)W) ? r2 : NEG_INF_D;
+                        double best = x0;
+                        int code = 0;
+                        if (x1 > best) {
+                            best = x1;
+                            code = 1;
+                        }
+                        if (x2 > best) {
+                            best = x2;
+                            code = 2;
+                        }
+                        nxt[j] = (best == NEG_INF_D) ? NEG_INF_D : best + (double)ev;
+                        bp[(size_t)t * W + j] = (uint8_t)code;
+                    }
+                }
+                if (more && f == fend - 1) stage_store((c + 1) & 1);    // (its last readers passed chunk c - 1's final barrier)
+                __syncthreads();
+                cur ^= 1;
+                ++t;
+                lo_prev = lo_t;
+            }
+        }
+        if (!dead) {
+            // every thread reads the same two cells: S-1 first, S-2 only if strictly better; each only inside the last band
+            const double* last = rowbuf + cur * W;
+            const int d = S - 1 - lo_prev;
+            if ((unsigned)d < (unsigned)W) {
+                final_v = last[(S - 1) & (W - 1)];
+                final_s = S - 1;
+            }
+            if (S > 1 && (unsigned)(d - 1) < (unsigned)W && last[(S - 2) & (W - 1)] > final_v) {
+                final_v = last[(S - 2) & (W - 1)];
+                final_s = S - 2;
+            }
+        }
+    } else if (!bad && tl == 0 && L == 0) {
+        final_v = 0.0;                                      // the empty path of an empty transcript
+    }
+    if (tid == 0) score[b] = final_v == final_v ? final_v : NEG_INF_D;
+    const bool feasible = final_v != NEG_INF_D && final_v == final_v;
+    if (!feasible || tl == 0) {
+        for (int t = tid; t < tl; t += NTHR) st_out[t] = -1;
+        for (int l = tid; l < L; l += NTHR) start_out[l] = end_out[l] = -1;
+        return;
+    }
+
+    // ---- back-trace: the pointer bytes were written by this workgroup's own waves.  A state on the path is in its frame's
+    // band, so its byte is the one in slot (state mod W) of that frame; the window's other bytes are never walked.
+    __threadfence();
+    __syncthreads();
+    int s_hi = final_s, after = -2;                         // state at frame t_hi - 1; state at frame t_hi (-2: none)
+    for (int t_hi = tl; t_hi > 0; t_hi -= BT_F) {
+        const int t_lo = max(0, t_hi - BT_F), n = t_hi - t_lo;
+        const int s_lo = max(0, s_hi - (BT_W - 1));
+        for (int idx = tid; idx < n * BT_W; idx += NTHR) {
+            const int f = idx / BT_W, col = s_lo + (idx % BT_W);
+            win[f][idx % BT_W] = (col <= s_hi) ? bp[(size_t)(t_lo + f) * W + (col & (W - 1))] : (uint8_t)0;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int w = s_hi;
+            path[n + 1] = after;
+            for (int f = n - 1; f >= 0; --f) {
+                path[1 + f] = w;
+                const int code = win[f][max(w - s_lo, 0)];  // (w >= s_hi - 2 (n - 1 - f) >= s_lo on a path; the clamp is for the index only)
+                w = max(w - min(code, 2), 0);               // the step below row 0 may leave the window: it is the next one's top
+            }
+            path[0] = t_lo > 0 ? w : -2;
+        }
+        __syncthreads();
+        for (int f = tid; f < n; f += NTHR) {
+            const int w = path[1 + f], t = t_lo + f;
+            st_out[t] = w;
+            if (w & 1) {
+                if (path[f] != w) start_out[w >> 1] = t;
+                if (path[2 + f] != w) end_out[w >> 1] = t;
+            }
+        }
+        after = path[1];
+        s_hi = path[0];
+        __syncthreads();
+    }
+}
+
+template <int W, int NTHR, int K>
+int launch(int B, hipStream_t st, const float* probs, const int32_t* sizes, const int32_t* labels,
+           const int32_t* label_offsets, const int32_t* label_lens, const int32_t* lo, int T, int A, int lmax, int blank,
+           int log_input, uint8_t* ws, int32_t* states, int32_t* starts, int32_t* ends, double* score) {
+    auto kernel = ctc_align_banded_kernel<W, NTHR, K>;
+    const size_t dyn = (size_t)2 * W * sizeof(double);
+    if (dyn + 20 * 1024 > 64 * 1024 &&                      // (the static part is 17 KiB)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) !=
+            hipSuccess) {
+        ds2_set_error("ds2_ctc_align_banded: %zu bytes of dynamic LDS are not available (band %d)", dyn, W);
+        return DS2_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(NTHR), dyn, st, probs, sizes, labels, label_offsets, label_lens, lo, T, A, lmax,
+                       blank, log_input, ws, states, starts, ends, score);
+    return DS2_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ds2_ctc_align_banded_ws_bytes(int B, int T, int band) {
+    if (B < 0 || T < 0 || band < 0) return 0;
+    return (size_t)B * T * band + 16;
+}
+
+extern "C" int ds2_ctc_align_banded(const float* probs, const int32_t* sizes, const int32_t* labels,
+                                    const int32_t* label_offsets, const int32_t* label_lens, const int32_t* lo, int B, int T,
+                                    int A, int max_label_len, int band, int blank, int log_input, void* ws, size_t ws_bytes,
+                                    int32_t* states, int32_t* starts, int32_t* ends, double* score, void* stream) {
+    if (band < BAND_MIN || band > BAND_MAX || (band & (band - 1)) != 0) {
+        ds2_set_error("ds2_ctc_align_banded: band %d is not a power of two in %d..%d", band, BAND_MIN, BAND_MAX);
+        return DS2_ERR_ARG;
+    }
+    if (max_label_len < 0 || max_label_len > (INT32_MAX - 1) / 2) {
+        ds2_set_error("ds2_ctc_align_banded: max_label_len %d is outside 0..%d (2 L + 1 states are counted in an int32)",
+                      max_label_len, (INT32_MAX - 1) / 2);
+        return DS2_ERR_ARG;
+    }
+    if (A < 1 || A > MAX_A) {
+        ds2_set_error("ds2_ctc_align_banded: alphabet size %d is outside 1..%d", A, MAX_A);
+        return DS2_ERR_ARG;
+    }
+    DS2_CHECK_ARG(B >= 0 && T >= 0 && blank >= 0 && blank < A);
+    if (B == 0) return DS2_OK;
+    // (labels may be NULL when every transcript is empty: it is read only below a positive label_lens[b])
+    DS2_CHECK_ARG(sizes && label_offsets && label_lens && score && (probs || T == 0) && (lo || T == 0));
+    DS2_CHECK_ARG((states || T == 0) && ((starts && ends) || max_label_len == 0));
+    if (ws_bytes < ds2_ctc_align_banded_ws_bytes(B, T, band) || !ws) {
+        ds2_set_error("ds2_ctc_align_banded: workspace of %zu bytes < ds2_ctc_align_banded_ws_bytes = %zu", ws_bytes,
+                      ds2_ctc_align_banded_ws_bytes(B, T, band));
+        return DS2_ERR_ARG;
+    }
+    int rc = DS2_OK;
+#define DS2_BANDED(W_, N_, K_)                                                                                         \
+    rc = launch<W_, N_, K_>(B, (hipStream_t)stream, probs, sizes, labels, label_offsets, label_lens, lo, T, A,          \
+                            max_label_len, blank, log_input, (uint8_t*)ws, states, starts, ends, score)
+    switch (band) {
+        case 64: DS2_BANDED(64, 256, 1); break;
+        case 128: DS2_BANDED(128, 256, 1); break;
+        case 256: DS2_BANDED(256, 256, 1); break;
+        case 512: DS2_BANDED(512, 512, 1); break;
+        case 1024: DS2_BANDED(1024, 1024, 1); break;
+        case 2048: DS2_BANDED(2048, 1024, 2); break;
+        case 4096: DS2_BANDED(4096, 1024, 4); break;
+        default: DS2_BANDED(8192, 1024, 8); break;
+    }
+#undef DS2_BANDED
+    if (rc != DS2_OK) return rc;
+    DS2_CHECK_LAUNCH();
+    return DS2_OK;
+}

@@ -878,6 +878,30 @@ def ctc_align(probs, sizes, labels, label_offsets, label_lens, max_label_len, bl
     return states, starts, ends, score
 
 
+def ctc_align_banded(probs, sizes, labels, label_offsets, label_lens, max_label_len, lo, band, blank=0, log_input=False):
+    """``ctc_align`` restricted to a moving band of ``band`` states per frame (``ds2_ctc_align_banded``): work and workspace
+    are T x band, so transcripts of any length align.  ``lo`` (B,T) int32 on the device, >= 0 and non-decreasing over an
+    utterance's frames: frame t admits the states lo[b,t] <= s < lo[b,t] + band.  ``band`` a power of two in
+    lib.ALIGN_BAND_MIN .. lib.ALIGN_BAND_MAX.  Returns states, starts, ends as ``ctc_align`` and score (B,) FLOAT64; an
+    utterance without an alignment inside its band (or with a bad band) has score -inf and -1 everywhere."""
+    for x in (probs, sizes, labels, label_offsets, label_lens, lo):
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+    bsz, t, a = probs.shape
+    if lo.dtype != torch.int32 or tuple(lo.shape) != (bsz, t):
+        raise RuntimeError('ctc_align_banded: lo must be int32 of shape (B,T) = (%d,%d)' % (bsz, t))
+    max_label_len, band = int(max_label_len), int(band)
+    ws_bytes = lib.query('ds2_ctc_align_banded_ws_bytes', bsz, t, band)
+    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
+    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
+    ends = torch.empty_like(starts)
+    score = torch.empty((bsz,), dtype=torch.float64, device=probs.device)
+    lib.call('ds2_ctc_align_banded', probs, sizes, labels, label_offsets, label_lens, lo, bsz, t, a, max_label_len, band,
+             int(blank), int(bool(log_input)), ws, ws.numel(), states, starts, ends, score)
+    return states, starts, ends, score
+
+
 # ----------------------------------------------------------------------------- CTC
 def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_len, grad_scale=1.0,
                   zero_batch_if_inf=False):

@@ -456,6 +456,35 @@ int ds2_ctc_align(const float* probs, const int32_t* sizes, const int32_t* label
                   const int32_t* label_lens, int B, int T, int A, int max_label_len, int blank, int log_input, void* ws,
                   size_t ws_bytes, int32_t* states, int32_t* starts, int32_t* ends, float* score, void* stream);
 
+/* ------------------------------------------------------------------ banded CTC alignment (csrc/ctc_align_banded.hip)
+ * Not in the reference.  ds2_ctc_align's quantity -- the same states, transitions, fp64 path scores, per-frame term and tie
+ * rule -- restricted to a moving band of W = band states per frame, so that work and workspace are T x W and a recording of
+ * an hour aligns to its whole transcript in one launch.  probs (B,T,A), sizes, labels / label_offsets / label_lens, blank,
+ * log_input, states (B,T), starts / ends (B,max_label_len) are as for ds2_ctc_align; there is no 511 limit on
+ * max_label_len, only 2 max_label_len + 1 < 2^31; A <= 256.  score (B) is FLOAT64 (an hour's path score is about -1e5).
+ * lo (B,T) int32 and band, a power of two in DS2_ALIGN_BAND_MIN .. DS2_ALIGN_BAND_MAX: at frame t < sizes[b] the admissible
+ * states are { s : lo[b][t] <= s < lo[b][t] + W, s < S = 2 L + 1 }.  The result is that of the full recursion in which
+ * v[t][s] is forced to -inf for every inadmissible s: a predecessor outside frame t-1's band counts as -inf, frame 0 starts
+ * from the virtual row that admits states 0 and 1 (if they are in its band), and the path must end in S-1 or S-2 inside the
+ * last frame's band.  With lo = 0 everywhere and W >= S the result is ds2_ctc_align's, bit for bit.
+ * lo must be >= 0, non-decreasing and rise by less than W from one of an utterance's valid frames to the next (consecutive
+ * bands share a state); this is checked on the device, and a violation makes THAT utterance "no alignment": score -inf and
+ * states / starts / ends all -1, as for a band that leaves no path and for every case ds2_ctc_align reports so.
+ * ws >= ds2_ctc_align_banded_ws_bytes(B, T, band) bytes: one back-pointer byte per frame and band slot (state s of frame t
+ * is kept in slot s mod W, which names one state of the band); need not be zeroed.
+ * Nothing past sizes[b] frames, past an utterance's labels or past its lo row's valid frames is read.  Results are
+ * bit-identical from run to run and depend neither on the batch's other utterances nor on the workspace's contents.
+ * DS2_ERR_ARG before any launch: band not a power of two or out of range; A, blank, B, T, max_label_len out of range; a
+ * workspace that is too small (the message names the needed size); NULL where data would be read.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_ALIGN_BAND_MIN 64
+#define DS2_ALIGN_BAND_MAX 8192
+size_t ds2_ctc_align_banded_ws_bytes(int B, int T, int band);
+int ds2_ctc_align_banded(const float* probs, const int32_t* sizes, const int32_t* labels, const int32_t* label_offsets,
+                         const int32_t* label_lens, const int32_t* lo, int B, int T, int A, int max_label_len, int band,
+                         int blank, int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts,
+                         int32_t* ends, double* score, void* stream);
+
 /* ------------------------------------------------------------------ voice-activity segmentation (csrc/vad.hip)
  * Not in the reference (it cuts its corpora with dataset scripts and sox).  Cuts a recording of any length into the clips the
  * model was trained on, from the int16 samples already on the device.  Integer arithmetic only: a result is exact.
