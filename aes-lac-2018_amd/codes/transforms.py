@@ -261,6 +261,96 @@ class ToTensor(object):
             self.__class__.__name__, self.sample_rate, self.augment, self.tempo_range, self.gain_range)
 
 
+def read_wav16(path, header_only=False):
+    """A 16-bit PCM WAV file of any rate and 1..8 channels -> ``(interleaved int16 numpy array, rate, channels)``.  Any other
+    sample width, compressed WAV and files that are not WAV raise ValueError with the file's name.  ``header_only``: check
+    the format and return ``(None, rate, channels)``."""
+    import wave
+
+    import numpy as np
+    try:
+        with wave.open(path, 'rb') as w:
+            channels, width, rate, comp = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getcomptype()
+            raw = b'' if header_only or width != 2 or comp != 'NONE' else w.readframes(w.getnframes())
+    except (wave.Error, EOFError) as e:
+        raise ValueError('%s: not a PCM WAV file (%s)' % (path, e))
+    if width != 2 or comp != 'NONE':
+        raise ValueError('%s: %d-bit samples; only 16-bit PCM is read (8-, 24- and 32-bit and float WAV are not)'
+                         % (path, 8 * width))
+    if not 1 <= channels <= ops.RESAMPLE_MAX_CHANNELS:
+        raise ValueError('%s: %d channels; 1 .. %d are read' % (path, channels, ops.RESAMPLE_MAX_CHANNELS))
+    if header_only:
+        return None, rate, channels
+    pcm = np.frombuffer(raw, dtype='<i2').astype(np.int16)
+    return pcm[:len(pcm) // channels * channels], rate, channels
+
+
+class Resample(object):
+    """Sample-rate conversion and downmix on the device (``ds2hip.ops.resample``, ``ds2_resample``): interleaved int16 of
+    any supported rate and 1..8 channels -> mono int16 at ``rate_out``, as a device tensor.  The filter is
+    ``ops.resample_design(rate_in, rate_out)``: a decision of this project, not parity with sox (README "Sample-rate
+    conversion").  A rate it has no filter for raises ``ValueError`` with the rate in the text.  Input at ``rate_out`` already
+    goes through the same launch with the identity filter: mono comes out bit for bit, several channels as their mean."""
+
+    def __init__(self, rate_out=16000, device='cuda'):
+        self.rate_out, self.device = int(rate_out), device
+
+    def batch(self, pcm, offsets, rate_in, channels=1):
+        """The flat form: clip b = pcm[offsets[b] : offsets[b + 1]] (int16 numpy array or tensor, uploaded if it is not on the
+        device yet) -> ``(out, out_offsets)``, one launch."""
+        ops.resample_design(rate_in, self.rate_out)                     # (an unsupported rate is refused before the upload)
+        pcm = torch.as_tensor(pcm)
+        if pcm.dtype != torch.int16 or pcm.dim() != 1:
+            raise ValueError('Resample takes 1-D int16 samples, got %s of shape %s' % (pcm.dtype, tuple(pcm.shape)))
+        return ops.resample(pcm.to(self.device).contiguous(), offsets, rate_in, self.rate_out, channels)
+
+    def __call__(self, pcm, rate_in, channels=1):
+        """One clip -> its mono int16 samples at ``rate_out`` on the device."""
+        pcm = torch.as_tensor(pcm)
+        return self.batch(pcm, [0, int(pcm.numel())], rate_in, channels)[0]
+
+    def __repr__(self):
+        return '{}(rate_out={})'.format(self.__class__.__name__, self.rate_out)
+
+
+def resample_files(paths, formats, rate_out, device):
+    """The files of a bank whose header ``formats[i] = (rate, channels)`` is not (``rate_out``, 1), converted on ``device``
+    with ONE launch per (rate, channels) group -> {path: mono int16 device tensor at rate_out}.  Files that need no
+    conversion are not read and not in the result."""
+    import numpy as np
+    groups = {}
+    for p, fmt in zip(paths, formats):
+        if tuple(fmt) != (rate_out, 1):
+            groups.setdefault(tuple(fmt), []).append(p)
+    out = {}
+    resampler = Resample(rate_out, device)
+    for (rate, channels), members in sorted(groups.items()):
+        parts = []
+        for p in members:
+            pcm, r, c = read_wav16(p)
+            if (r, c) != (rate, channels):
+                raise ValueError('{} is now {} Hz with {} channel(s), its header said {} Hz and {}'.format(p, r, c, rate, channels))
+            parts.append(pcm)
+        offsets = np.concatenate([[0], np.cumsum([len(a) for a in parts])]).tolist()
+        flat, out_off = resampler.batch(np.concatenate(parts), offsets, rate, channels)
+        for i, p in enumerate(members):
+            out[p] = flat[out_off[i]:out_off[i + 1]]
+    return out
+
+
+def _converted_frames(what, path, rate, width, chans, frames, rate_out):
+    """A bank file that ``resample=True`` converts: refuse by name what cannot be converted (another sample width, more than
+    eight channels, a rate without a filter) and return its length in samples at ``rate_out``."""
+    if width != 2 or not 1 <= chans <= ops.RESAMPLE_MAX_CHANNELS:
+        raise ValueError('{} {}: {} Hz, {} bit, {} channel(s); only 16-bit PCM with 1 .. {} channels is converted'.format(
+            what, path, rate, 8 * width, chans, ops.RESAMPLE_MAX_CHANNELS))
+    try:
+        L, M, _ = ops.resample_design(rate, rate_out)
+    except ValueError as e:
+        raise ValueError('{} {}: {}'.format(what, path, e))
+    return ops.resample_out_len(frames, L, M)
+
+
 def noise_start(u, noise_len, n):
     """First sample of the noise crop for a clip of ``n`` samples, from the uniform draw ``u`` in [0, 1): the reference's
     ``torch.rand(()) * (noise_len - signal_len)`` in samples when the recording is at least as long as the clip (the crop
@@ -280,7 +370,9 @@ class NoiseInjection(object):
 
     * ``path`` is searched recursively for ``.wav`` files, in sorted order (a missing directory raises ``IOError``, as in
       the reference).  Every file must be 16-bit mono PCM at ``sample_rate``: the reference resamples and downmixes through
-      sox, which is not available here, so any other file is REFUSED by name -- convert the noise set once, offline.  An
+      sox, which is not available here, so any other file is REFUSED by name -- convert the noise set once, offline
+      (tools/resample_wav.py), or pass ``resample=True``: 16-bit files at another rate or with up to eight channels are then
+      converted on the device when the bank is built (``resample_files``: one launch per (rate, channels) group).  An
       empty directory and a zero-length file are refused; a set longer than ``max_bank_seconds`` (one hour = 115 MB of
       int16 per GPU) raises ``ValueError`` rather than being truncated.
     * with probability ``prob`` a clip gets noise.  ``draw()`` -- what a loader worker calls -- returns None or
@@ -301,13 +393,14 @@ class NoiseInjection(object):
     (``ops.amplitude_scale``: the noise goes through the same conversion as the speech)."""
 
     def __init__(self, path, sample_rate=16000, noise_levels=(0, 0.5), prob=0.4, device='cuda', max_bank_seconds=3600,
-                 scale=None):
+                 scale=None, resample=False):
         import os
         import threading
         import wave
         if path is None or not os.path.isdir(path):
             raise IOError('Directory does not exist: {}'.format(path))
         self.path, self.sample_rate, self.prob = path, int(sample_rate), float(prob)
+        self.resample = bool(resample)
         self.noise_levels = (float(noise_levels[0]), float(noise_levels[1]))
         self.device, self.max_bank_seconds = device, max_bank_seconds
         self.scale = ops.amplitude_scale(scale)
@@ -315,19 +408,22 @@ class NoiseInjection(object):
                             if f.lower().endswith('.wav'))
         if not self.paths:
             raise ValueError('no .wav file under the noise directory {}'.format(path))
-        self.lengths = []
+        self.lengths, self.formats = [], []          # (lengths: in samples of the bank, i.e. after a conversion)
         for p in self.paths:
             try:
                 with wave.open(p, 'rb') as w:
                     rate, width, chans, frames = w.getframerate(), w.getsampwidth(), w.getnchannels(), w.getnframes()
             except (wave.Error, EOFError) as e:
                 raise ValueError('noise file {} is not a PCM WAV file: {}'.format(p, e))
-            if rate != self.sample_rate or width != 2 or chans != 1:
+            if self.resample and (rate != self.sample_rate or chans != 1):
+                frames = _converted_frames('noise file', p, rate, width, chans, frames, self.sample_rate)
+            elif rate != self.sample_rate or width != 2 or chans != 1:
                 raise ValueError('noise file {}: {} Hz, {} bit, {} channel(s); the noise bank takes 16-bit mono PCM at {} Hz '
                                  'only (nothing is resampled here: convert the file)'.format(p, rate, 8 * width, chans,
                                                                                             self.sample_rate))
             if frames <= 0:
                 raise ValueError('noise file {} holds no samples'.format(p))
+            self.formats.append((rate, chans))
             self.lengths.append(int(frames))
         total = sum(self.lengths)
         if total > max_bank_seconds * self.sample_rate:
@@ -373,11 +469,14 @@ class NoiseInjection(object):
             bank = self._banks.get(device)
             if bank is None:
                 loader = ToTensor(sample_rate=self.sample_rate)
-                parts = [loader._load(p) for p in self.paths]
+                # (resample=True: the files at another rate or channel count, one launch per (rate, channels) group)
+                conv = resample_files(self.paths, self.formats, self.sample_rate, device) if self.resample else {}
+                parts = [conv[p] if p in conv else loader._load(p) for p in self.paths]
                 for p, part, n in zip(self.paths, parts, self.lengths):
                     if part.numel() != n:
                         raise ValueError('noise file {} holds {} samples, its header says {}'.format(p, part.numel(), n))
-                bank = self._banks[device] = torch.cat(parts).to(device)
+                bank = self._banks[device] = torch.cat([part.to(device) for part in parts]) if conv else \
+                    torch.cat(parts).to(device)
         return bank
 
     def params(self, draws, lens):
@@ -442,7 +541,9 @@ class Reverb(object):
 
     * ``path`` is searched recursively for ``.wav`` files, in sorted order (a missing directory raises ``IOError``).  Every
       file must be 16-bit mono PCM at ``sample_rate`` = 16000; any other file is REFUSED by name -- another rate, width or
-      channel count, an empty or all-zero file -- and so is an empty directory.  Nothing is resampled.
+      channel count, an empty or all-zero file -- and so is an empty directory.  Nothing is resampled, unless
+      ``resample=True``: 16-bit files at another rate or with up to eight channels are then converted to 16 kHz mono on the
+      device when the object is built (one launch per (rate, channels) group) and the rule below runs on the int16 result.
     * per file (``rir_from_pcm``): the RIR starts at the file's largest |sample| and is divided by it, so ``h[0] == 1`` and the
       direct path is not delayed; what precedes the peak is dropped; at most ``int(max_rir_seconds * 16000)`` taps are kept,
       trailing zeros are stripped.  A set with more than ``max_bank_seconds`` of taps in total raises ``ValueError`` rather
@@ -459,7 +560,8 @@ class Reverb(object):
     decode, tempo and gain, before the noise.  ``__call__(x)`` is the per-clip contract through the same kernel (a CPU
     tensor makes a GPU round trip)."""
 
-    def __init__(self, path, sample_rate=16000, prob=0.3, max_rir_seconds=0.5, max_bank_seconds=600, device='cuda'):
+    def __init__(self, path, sample_rate=16000, prob=0.3, max_rir_seconds=0.5, max_bank_seconds=600, device='cuda',
+                 resample=False):
         import os
         import threading
         import wave
@@ -471,7 +573,7 @@ class Reverb(object):
             raise ValueError('Reverb: prob must lie in [0, 1], got %r' % (prob,))
         self.path, self.sample_rate, self.prob = path, int(sample_rate), float(prob)
         self.max_rir_seconds, self.max_bank_seconds = max_rir_seconds, max_bank_seconds
-        self.device = device
+        self.device, self.resample = device, bool(resample)
         self.max_taps = int(max_rir_seconds * self.sample_rate)
         if not 1 <= self.max_taps <= ops.REVERB_MAX_TAPS:
             raise ValueError('Reverb: max_rir_seconds = %r is %d taps; the kernel takes 1..%d'
@@ -484,19 +586,28 @@ class Reverb(object):
         # the trailing zeros begin decide a file's tap count, which the size limit and ``params`` need, and an all-zero file
         # is refused here, before training starts, not at the first batch.  The taps are not kept: the bank is built on
         # first use in the process that owns the GPU
-        self.lengths = []
+        # resample=True: the files at another rate or channel count are converted on the device HERE, one launch per (rate,
+        # channels) group, and their 16 kHz samples (an RIR is short) are kept on the host for the rule above
+        self.lengths, self._converted, formats = [], {}, []
         for p in self.paths:
             try:
                 with wave.open(p, 'rb') as w:
                     rate, width, chans, frames = w.getframerate(), w.getsampwidth(), w.getnchannels(), w.getnframes()
             except (wave.Error, EOFError) as e:
                 raise ValueError('RIR file {} is not a PCM WAV file: {}'.format(p, e))
-            if rate != self.sample_rate or width != 2 or chans != 1:
+            if self.resample and (rate != self.sample_rate or chans != 1):
+                _converted_frames('RIR file', p, rate, width, chans, frames, self.sample_rate)
+            elif rate != self.sample_rate or width != 2 or chans != 1:
                 raise ValueError('RIR file {}: {} Hz, {} bit, {} channel(s); the RIR bank takes 16-bit mono PCM at {} Hz '
                                  'only (nothing is resampled here: convert the file)'.format(p, rate, 8 * width, chans,
                                                                                             self.sample_rate))
             if frames <= 0:
                 raise ValueError('RIR file {} holds no samples'.format(p))
+            formats.append((rate, chans))
+        if self.resample:
+            self._converted = {p: t.cpu().numpy() for p, t in
+                               resample_files(self.paths, formats, self.sample_rate, device).items()}
+        for p in self.paths:
             self.lengths.append(int(self._taps(p).size))
         total = sum(self.lengths)
         if total > max_bank_seconds * self.sample_rate:
@@ -512,8 +623,11 @@ class Reverb(object):
         import wave
 
         import numpy as np
-        with wave.open(p, 'rb') as w:
-            pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+        if p in self._converted:
+            pcm = self._converted[p]
+        else:
+            with wave.open(p, 'rb') as w:
+                pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
         try:
             return rir_from_pcm(pcm, self.max_taps)
         except ValueError as e:

@@ -65,26 +65,29 @@ def audio_scale(config):
 
 def get_noise(data_dir, config, scale=None):
     """``training.noise`` of the JSON config (an addition to the reference's schema, whose NoiseInjection no config reaches):
-    ``{"path": DIR, "noise_levels": [lo, hi], "prob": p}`` -> a ``transforms.NoiseInjection`` (None without the block).
+    ``{"path": DIR, "noise_levels": [lo, hi], "prob": p}`` -> a ``transforms.NoiseInjection`` (None without the block);
+    ``"resample": true`` converts files at another rate or channel count when the bank is built (the default refuses them).
     Independent of ``training.augment``; a relative ``path`` that does not exist from the working directory is looked up
     under ``--data-dir``.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""
     training = config.get('training', {}) if hasattr(config, 'get') else {}
     block = (training or {}).get('noise', None)
     if not block:
         return None
-    unknown = set(block) - {'path', 'noise_levels', 'prob', 'max_bank_seconds'}
+    unknown = set(block) - {'path', 'noise_levels', 'prob', 'max_bank_seconds', 'resample'}
     if unknown or 'path' not in block:
-        raise ValueError('training.noise takes path (required), noise_levels, prob, max_bank_seconds; got %s' % sorted(block))
-    kwargs = {k: block[k] for k in ('noise_levels', 'prob', 'max_bank_seconds') if k in block}
+        raise ValueError('training.noise takes path (required), noise_levels, prob, max_bank_seconds, resample; got %s'
+                         % sorted(block))
+    kwargs = {k: block[k] for k in ('noise_levels', 'prob', 'max_bank_seconds', 'resample') if k in block}
     return transforms.NoiseInjection(_resolve(block['path'], data_dir), scale=scale, **kwargs)
 
 
-REVERB_KEYS = ('path', 'prob', 'max_rir_seconds', 'max_bank_seconds')
+REVERB_KEYS = ('path', 'prob', 'max_rir_seconds', 'max_bank_seconds', 'resample')
 
 
 def get_reverb(data_dir, config):
     """``training.reverb`` of the JSON config (an addition to the reference's schema): ``{"path": DIR, "prob": p,
-    "max_rir_seconds": s, "max_bank_seconds": S}`` -> a ``transforms.Reverb`` (None without the block).  ``path`` is required;
+    "max_rir_seconds": s, "max_bank_seconds": S, "resample": false}`` -> a ``transforms.Reverb`` (None without the block;
+    ``"resample": true`` converts files at another rate or channel count, the default refuses them).  ``path`` is required;
     keys left out keep the constructor's defaults; an unknown key is refused by name.  Independent of ``training.augment``,
     ``training.noise`` and ``training.spec_augment``; a relative ``path`` that does not exist from the working directory is
     looked up under ``--data-dir``.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""

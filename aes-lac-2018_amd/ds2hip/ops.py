@@ -240,6 +240,111 @@ def reverb(wav, offsets, bank, rir_lo, rir_len, keep_level=True, out=None, retur
     return (out, gain) if return_gain else out
 
 
+RESAMPLE_TILE = 1024                    # DS2_RESAMPLE_TILE of include/ds2hip.h: outputs of one clip per workgroup tile
+RESAMPLE_MAX_L, RESAMPLE_MAX_M, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_CHANNELS = 1024, 4096, 1023, 8      # ds2_resample's limits
+RESAMPLE_RATES = (4000, 192000)         # input rates resample_design takes
+
+_resample_designs = {}
+
+
+def resample_design(rate_in, rate_out=16000, zeros=24, rolloff=0.95, beta=9.0):
+    """The polyphase filter of a conversion ``rate_in`` -> ``rate_out``: ``(L, M, taps)`` with L / M the reduced ratio and taps
+    an (L, K) float32 array, K odd, for ``ds2_resample``.  A Kaiser-windowed sinc with ``zeros`` zero crossings on either
+    side, cut off at ``rolloff`` times the lower Nyquist frequency; computed in float64 on the host, rounded to float32 once
+    and cached per argument tuple.  The defaults are a decision of this project, not parity with sox (include/ds2hip.h)."""
+    import math
+    import numpy as np
+    key = (rate_in, rate_out, zeros, rolloff, beta)
+    if key in _resample_designs:
+        return _resample_designs[key]
+    if isinstance(rate_in, bool) or int(rate_in) != rate_in or not RESAMPLE_RATES[0] <= rate_in <= RESAMPLE_RATES[1]:
+        raise ValueError('resample: a sample rate of %r Hz is not supported (%d .. %d Hz)' % ((rate_in,) + RESAMPLE_RATES))
+    if isinstance(rate_out, bool) or int(rate_out) != rate_out or rate_out < 1 or zeros < 1 or not 0 < rolloff <= 1:
+        raise ValueError('resample: cannot design a filter for %r Hz out, %r zero crossings, roll-off %r'
+                         % (rate_out, zeros, rolloff))
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    g = math.gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    if L > RESAMPLE_MAX_L or M > RESAMPLE_MAX_M:
+        raise ValueError('resample: a sample rate of %d Hz is not supported: %d Hz is %d / %d of it, and the filter bank '
+                         'takes ratios up to %d / %d' % (rate_in, rate_out, L, M, RESAMPLE_MAX_L, RESAMPLE_MAX_M))
+    if L == M:                                   # equal rates: the identity (one tap of 1), so only the downmix is left
+        taps = np.ones((1, 1), np.float32)
+        taps.setflags(write=False)
+        _resample_designs[key] = (1, 1, taps)
+        return _resample_designs[key]
+    c = rolloff * min(1.0, L / M)
+    half = int(math.ceil(zeros / c))
+    K = 2 * half + 1
+    if K > RESAMPLE_MAX_TAPS:
+        raise ValueError('resample: a sample rate of %d Hz is not supported: its filter has %d taps per phase, more than %d'
+                         % (rate_in, K, RESAMPLE_MAX_TAPS))
+    u = (np.arange(K, dtype=np.float64)[None, :] - half) - np.arange(L, dtype=np.float64)[:, None] / L
+    a = np.abs(u) * c / zeros
+    win = np.i0(beta * np.sqrt(np.maximum(1.0 - a * a, 0.0))) / np.i0(beta)
+    taps = np.where(a > 1.0, 0.0, c * np.sinc(c * u) * win).astype(np.float32)
+    taps.setflags(write=False)
+    _resample_designs[key] = (L, M, taps)
+    return _resample_designs[key]
+
+
+def resample_out_len(n_frames, L, M):
+    """ds2_resample_out_len: outputs of a clip of ``n_frames`` frames at the ratio L / M."""
+    return (int(n_frames) * L + M - 1) // M
+
+
+_resample_taps_dev = {}
+
+
+def resample(pcm, offsets, rate_in, rate_out=16000, channels=1, taps=None):
+    """Sample-rate conversion and downmix for a flat buffer of clips in one launch on the current stream (``ds2_resample``).
+    pcm: 1-D int16 on the device, clip b = pcm[offsets[b] : offsets[b + 1]] with ``channels`` interleaved channels;
+    offsets: python sequence (B+1), in elements.  ``taps``: None for ``resample_design(rate_in, rate_out)``, or ``(L, M, taps)``
+    with taps an (L, K) float32 array or device tensor.  Returns ``(out, out_offsets)``: the mono int16 clips at ``rate_out``,
+    concatenated in a new device tensor, and their offsets as a python list."""
+    import numpy as np
+    if not isinstance(pcm, torch.Tensor) or not pcm.is_cuda or pcm.dtype != torch.int16 or pcm.dim() != 1:
+        raise RuntimeError('resample takes a 1-D int16 tensor on the device')
+    if not pcm.is_contiguous():
+        raise RuntimeError('ds2hip entry points take contiguous tensors')
+    channels = int(channels)
+    if not 1 <= channels <= RESAMPLE_MAX_CHANNELS:
+        raise ValueError('resample: %d channels, not 1 .. %d' % (channels, RESAMPLE_MAX_CHANNELS))
+    if taps is None:
+        L, M, table = resample_design(rate_in, rate_out)
+        key = (rate_in, rate_out, pcm.device)
+        taps_d = _resample_taps_dev.get(key)
+        if taps_d is None:
+            taps_d = _resample_taps_dev[key] = torch.from_numpy(np.array(table)).to(pcm.device)
+    else:
+        L, M, table = taps
+        L, M = int(L), int(M)
+        taps_d = table if isinstance(table, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(table, np.float32))
+        if taps_d.dtype != torch.float32 or taps_d.dim() != 2 or taps_d.shape[0] != L:
+            raise ValueError('resample: taps must be an (L, K) float32 table, L = %d' % L)
+        taps_d = taps_d.to(pcm.device).contiguous()
+    K = int(taps_d.shape[1])
+    if not (1 <= L <= RESAMPLE_MAX_L and 1 <= M <= RESAMPLE_MAX_M and 1 <= K <= RESAMPLE_MAX_TAPS and K % 2 == 1):
+        raise ValueError('resample: ratio %d / %d with %d taps per phase; L in 1..%d, M in 1..%d, taps odd in 1..%d'
+                         % (L, M, K, RESAMPLE_MAX_L, RESAMPLE_MAX_M, RESAMPLE_MAX_TAPS))
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    bsz = len(off) - 1
+    if not 1 <= bsz <= 65535:
+        raise ValueError('resample: %d clips, not 1 .. 65535' % bsz)
+    lens = np.diff(off)
+    if off[0] < 0 or (lens < 0).any() or off[-1] > pcm.numel():
+        raise ValueError('resample: offsets do not describe clips inside the sample buffer')
+    if (lens % channels != 0).any():
+        b = int(np.argmax(lens % channels != 0))
+        raise ValueError('resample: clip %d holds %d samples, not a whole number of %d-channel frames' % (b, lens[b], channels))
+    out_off = np.concatenate([[0], np.cumsum((lens // channels * L + M - 1) // M)]).astype(np.int64)
+    out = torch.empty((int(out_off[-1]),), dtype=torch.int16, device=pcm.device)
+    if out_off[-1] > 0:
+        meta_d = upload_small(torch.from_numpy(np.concatenate([off, out_off])), pcm.device)      # one upload
+        lib.call('ds2_resample', pcm, meta_d[:bsz + 1], bsz, channels, L, M, taps_d, K, out, meta_d[bsz + 1:])
+    return out, [int(v) for v in out_off]
+
+
 VAD_BLOCK = 160                         # DS2_VAD_BLOCK of include/ds2hip.h: samples per block of ds2_vad_segment (10 ms)
 VAD_BINS = 192                          # DS2_VAD_BINS: level bins
 

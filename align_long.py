@@ -4,7 +4,7 @@ reference, whose data scripts only consume corpora that somebody already cut).
 
     python align_long.py --model-path CKPT (--audio A.wav [B.wav ...] --transcript A.txt [B.txt ...] |
                          --manifest M.csv [--data-dir DIR]) --output-path OUT.jsonl [--batch-size 32]
-                         [--band-states 4096 --band-margin 16]
+                         [--band-states 4096 --band-margin 16] [--resample]
                          [--clips-dir DIR --clips-manifest FILE --min-score-per-frame X]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
@@ -30,7 +30,10 @@ clean, has a text and scores at or above X as ``DIR/<audio stem>_<k:05d>.wav`` (
 format ``codes.data.AudioDataset`` reads.  There is NO default threshold: nobody has measured what value separates good clips
 from bad on a trained model.  Audio that the transcript does not cover (announcements, music) is force-aligned all the same
 and shows up only as low segment scores; skipping audio or text, resampling and other sample formats are out of scope.
-Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name before any work is done."""
+Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name before any work is done -- unless ``--resample``
+is given, as in transcribe.py: a 16-bit PCM WAV of any supported rate and 1..8 channels is converted to 16 kHz mono on the
+device before it is segmented, the record gains ``source_rate`` and ``source_channels``, every time refers to the 16 kHz
+samples, and ``--clips-dir`` writes the CONVERTED samples (16 kHz mono, what train.py reads)."""
 import argparse
 import json
 import math
@@ -46,7 +49,7 @@ sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 sys.path.insert(0, ROOT)
 
 from codes.align import ForcedAligner, LongAligner  # noqa: E402
-from transcribe import SAMPLE_RATE, batch_order, read_pcm16  # noqa: E402
+from transcribe import SAMPLE_RATE, batch_order, read_pcm16, read_source, source_samples  # noqa: E402,F401
 
 
 def normalised_transcript(path):
@@ -163,6 +166,8 @@ def main(argv=None):
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument('--audio', nargs='+', metavar='WAV', help='16-bit mono PCM WAV files at 16 kHz, of any length')
     src.add_argument('--manifest', metavar='CSV', help='rows of audio_path,transcript_path[,...]')
+    p.add_argument('--resample', action='store_true',
+                   help='take 16-bit PCM WAV of any supported rate and 1..8 channels: converted to 16 kHz mono on the device')
     p.add_argument('--transcript', nargs='+', metavar='TXT', help='one transcript file per --audio file, in its order')
     p.add_argument('--data-dir', help='directory that relative --manifest paths (and the label files) are found in')
     p.add_argument('--model-path', default='models/deepspeech_final.pth')
@@ -207,7 +212,7 @@ def main(argv=None):
         files = [(r[0], find(r[0]), find(r[1])) for r in rows]
 
     from codes.segment import Segmenter
-    from codes.transforms import BatchSpectrogram, waveform_scale
+    from codes.transforms import BatchSpectrogram, Resample, waveform_scale
     from codes.utils.model_utils import checkpoint_langs, load_model
     try:
         segmenter = Segmenter(max_segment=args.max_segment, min_speech=args.min_speech, min_silence=args.min_silence,
@@ -217,7 +222,7 @@ def main(argv=None):
         p.error(str(e))
     for _, path, txt in files:                              # a file that will be refused is refused before any work
         try:
-            read_pcm16(path, header_only=True)
+            read_source(path, args.resample, header_only=True)
         except (ValueError, OSError) as e:
             raise SystemExit('align_long.py: ' + str(e))
         if not os.path.isfile(txt):
@@ -234,6 +239,7 @@ def main(argv=None):
     target_t = target_t[0]
     aligner = LongAligner(target_t.label_encoder, band_states=args.band_states, band_margin=args.band_margin)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
+    resampler = Resample(SAMPLE_RATE, device='cuda') if args.resample else None
     if args.clips_dir is not None:
         os.makedirs(args.clips_dir, exist_ok=True)
 
@@ -241,16 +247,19 @@ def main(argv=None):
     with open(args.output_path, 'w') as out_f:
         for name, path, txt in files:
             try:
-                samples = read_pcm16(path)
+                samples, source = source_samples(path, args.resample, resampler)
             except ValueError as e:
                 raise SystemExit('align_long.py: ' + str(e))
             # (ToLabel given a PATH reads its first line only; the whole file goes in as a string)
             labels = target_t(normalised_transcript(txt)).reshape(-1)
             rec, blocks = align_samples(name, samples, labels, model, frontend, segmenter, aligner, args.batch_size)
+            rec.update(source)
             n_seg += len(rec['segments'])
             out_f.write(json.dumps(rec) + '\n')
             out_f.flush()
             if args.clips_dir is not None and rec['score'] is not None:
+                if torch.is_tensor(samples):                # (--resample: the converted samples come back for the clips)
+                    samples = samples.cpu().numpy()
                 clip_rows += write_clips(rec, blocks, samples, path, args.clips_dir, args.data_dir, args.min_score_per_frame)
     if args.clips_manifest is not None:
         with open(args.clips_manifest, 'w') as f:

@@ -154,6 +154,37 @@ size_t ds2_reverb_ws_bytes(int B, size_t max_clip_len);
 int ds2_reverb(const float* wav, const int64_t* offsets, int B, const float* bank, const int64_t* rir_lo,
                const int64_t* rir_len, int keep_level, float* out, float* gain, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ sample-rate conversion (csrc/resample.hip)
+ * 16-bit PCM of any rate and 1..8 channels to mono at another rate, before everything above: the reference handed its files
+ * to sox, which is not part of this project.  Nothing here is parity with sox: the filter (host, ds2hip/ops.py
+ * resample_design: a Kaiser-windowed sinc, 24 zero crossings, roll-off 0.95, beta 9) and every rule below are decisions,
+ * and nobody has measured their effect on WER.
+ *   pcm, in_offsets   clip b = pcm[in_offsets[b] .. in_offsets[b+1]) holds n_b = (in_offsets[b+1] - in_offsets[b]) / channels
+ *                     interleaved frames; (B+1) int64 on the device.  A length that is not a multiple of `channels` (or a
+ *                     negative one) is DS2_ERR_ARG and nothing is written
+ *   taps              (L, K) float32, K odd, h = (K - 1) / 2: row p is the filter at the fractional position p / L
+ * Downmix:  s[j] = sum_c pcm[in_offsets[b] + j * channels + c], an exact integer (|s| <= 2^18), exact as a float.
+ * Polyphase FIR:  for output m in [0, ds2_resample_out_len(n_b, L, M)):  t = m * M (int64: an hour at M = 441 passes 2^31),
+ * i0 = t / L, p = t % L,  y = sum_{k=0}^{K-1} taps[p * K + k] * s[i0 + k - h],  where s outside [0, n_b) is zero -- never the
+ * neighbouring clip of the flat buffer, and nothing outside the clip is loaded.  The sum is ONE chain of fused multiply-adds
+ * in one fp32 accumulator that starts at +0 and takes k = 0, 1, .. K - 1 in that order, the zero products of the padding
+ * included (they change no bit while the taps are finite); the order does not depend on the grid, the tile or the batch.
+ * Output:  v = y * (1.0f / channels), one rounded multiply, skipped for one channel;
+ * out[out_offsets[b] + m] = (int16) clamp(rint(v), -32768, 32767), rounding half to even.  Elements of out outside every
+ * clip are not written; out must not overlap pcm.
+ * One kernel, no atomics, no workspace: a workgroup produces DS2_RESAMPLE_TILE consecutive outputs of one clip (tiles counted
+ * from the clip's own start) and stages the downmixed span of the tile through LDS.  A clip's output bits depend on the clip
+ * and the taps only -- not on B, on its position in the batch or in memory, or on the other clips.
+ * L = M = K = 1, taps = [1], channels = 1 copies the input bit for bit.
+ * Limits (DS2_ERR_ARG outside them): B in 1..65535, channels in 1..8, L in 1..1024, M in 1..4096, K odd in 1..1023.
+ * Unlike the other entry points this one WAITS on `stream` once before its launch: it reads the B + 1 input offsets back, to
+ * check the lengths before anything is written and to size the grid by the longest clip.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_RESAMPLE_TILE 1024
+size_t ds2_resample_out_len(size_t n_frames, int L, int M);      /* (n_frames * L + M - 1) / M */
+int ds2_resample(const int16_t* pcm, const int64_t* in_offsets, int B, int channels, int L, int M, const float* taps, int K,
+                 int16_t* out, const int64_t* out_offsets, void* stream);
+
 /* ------------------------------------------------------------------ SpecAugment
  * Time warp, frequency masks and time masks on the log-spectrogram of a minibatch, one launch, between ds2_spectrogram_fwd and
  * the model.  The reference has no such stage (its augmentation is tempo, gain and noise, all on the waveform): nothing here is

@@ -3,7 +3,7 @@
 
     python transcribe.py --model-path CKPT (--audio A.wav [B.wav ...] | --manifest M.csv [--data-dir DIR])
                          --output-path OUT.jsonl [--batch-size 32] [--decoder greedy|beam] [--beam-width W]
-                         [--lm-path F --lm-unit U --alpha A --beta B] [--beam-device]
+                         [--lm-path F --lm-unit U --alpha A --beta B] [--beam-device] [--resample]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
 
@@ -14,7 +14,10 @@ input order: ``path``, ``duration``, ``noise_floor_db``, ``threshold_db``, ``spe
 joined by one space) and ``segments``, a list of ``{start, end, text, words: [{word, start, end}]}`` with times in seconds
 rounded to 3 decimals.  A word spans its first to its last character; a character's time is the segment's start plus the
 centre of the model output step the decoder reports for it.  Model loading, amplitude scale, frontend and decoders are
-test.py's.  Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name (there is no resampling)."""
+test.py's.  Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name (there is no resampling) -- unless
+``--resample`` is given: a 16-bit PCM WAV of any supported rate and 1..8 channels is then uploaded as it is and converted to
+16 kHz mono on the device (``codes.transforms.Resample``, ``ds2_resample``) before it is segmented; the record gains
+``source_rate`` and ``source_channels``, and ``duration`` and all times refer to the 16 kHz samples."""
 import argparse
 import json
 import os
@@ -48,6 +51,31 @@ def read_pcm16(path, header_only=False):
     if width != 2 or comp != 'NONE':
         raise ValueError('%s: %d-bit samples; transcribe.py takes 16-bit PCM only' % (path, 8 * width))
     return None if header_only else np.frombuffer(raw, dtype='<i2').astype(np.int16)
+
+
+def read_source(path, resample, header_only=False):
+    """What ``--resample`` changes about reading a file: without it ``read_pcm16`` and its refusals; with it any 16-bit PCM
+    WAV of 1..8 channels whose rate has a filter (``ops.resample_design``), an unsupported rate being refused by name.
+    Returns ``(samples as stored in the file or None, rate, channels)``."""
+    if not resample:
+        return read_pcm16(path, header_only), SAMPLE_RATE, 1
+    from codes.transforms import read_wav16
+    from ds2hip import ops
+    samples, rate, channels = read_wav16(path, header_only)
+    try:
+        ops.resample_design(rate, SAMPLE_RATE)
+    except ValueError as e:
+        raise ValueError('%s: %s' % (path, e))
+    return samples, rate, channels
+
+
+def source_samples(path, resample, resampler=None):
+    """The recording as 16 kHz mono int16 -- the file's own samples, or with ``--resample`` the device tensor the conversion
+    leaves -- and the fields the record gains."""
+    samples, rate, channels = read_source(path, resample)
+    if not resample:
+        return samples, {}
+    return resampler(samples, rate, channels), {'source_rate': rate, 'source_channels': channels}
 
 
 def batch_order(blocks, batch_size):
@@ -105,6 +133,8 @@ def main(argv=None):
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument('--audio', nargs='+', metavar='WAV', help='16-bit mono PCM WAV files at 16 kHz, of any length')
     src.add_argument('--manifest', metavar='CSV', help='a manifest whose first column names the files')
+    p.add_argument('--resample', action='store_true',
+                   help='take 16-bit PCM WAV of any supported rate and 1..8 channels: converted to 16 kHz mono on the device')
     p.add_argument('--data-dir', help='directory that relative --manifest paths (and the label files) are found in')
     p.add_argument('--model-path', default='models/deepspeech_final.pth')
     p.add_argument('--output-path', required=True, type=str, help='JSON lines, one per input file')
@@ -135,7 +165,7 @@ def main(argv=None):
 
     from codes.decoder import BeamCTCDecoder, DeviceBeamCTCDecoder, GreedyDecoder
     from codes.segment import Segmenter
-    from codes.transforms import BatchSpectrogram, waveform_scale
+    from codes.transforms import BatchSpectrogram, Resample, waveform_scale
     from codes.utils.model_utils import checkpoint_langs, load_model
     try:
         segmenter = Segmenter(max_segment=args.max_segment, min_speech=args.min_speech, min_silence=args.min_silence,
@@ -152,7 +182,7 @@ def main(argv=None):
                  for name in names]
     for _, path in files:                                   # a file that will be refused is refused before any work
         try:
-            read_pcm16(path, header_only=True)
+            read_source(path, args.resample, header_only=True)
         except (ValueError, OSError) as e:
             raise SystemExit('transcribe.py: ' + str(e))
 
@@ -177,15 +207,17 @@ def main(argv=None):
     else:
         decoder = BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
+    resampler = Resample(SAMPLE_RATE, device='cuda') if args.resample else None
 
     n_seg = 0
     with open(args.output_path, 'w') as out_f:
         for name, path in files:
             try:
-                samples = read_pcm16(path)
+                samples, source = source_samples(path, args.resample, resampler)
             except ValueError as e:
                 raise SystemExit('transcribe.py: ' + str(e))
             rec = transcribe_samples(name, samples, model, frontend, decoder, segmenter, args.batch_size)
+            rec.update(source)
             n_seg += len(rec['segments'])
             out_f.write(json.dumps(rec) + '\n')
             out_f.flush()
