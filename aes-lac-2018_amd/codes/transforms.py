@@ -58,12 +58,14 @@ class BatchSpectrogram(object):
     clip's frames, percentage = T_i / float(T_max) stored as float32.
     """
 
-    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None, spec_augment=None, reverb=None):
+    def __init__(self, normalize=True, eps=1e-9, device='cuda', scale=None, noise=None, spec_augment=None, reverb=None,
+                 speed=None):
         self.normalize, self.eps, self.device = normalize, eps, device
         self.scale = ops.amplitude_scale(scale)      # int16 clips (RawAudioBatch) come out as q * scale: see ToTensor
         self.noise = noise                           # a NoiseInjection: the bank the drawn noise of a batch is mixed from
         self.spec_augment = spec_augment             # a SpecAugment: resolves and applies the draws a batch carries
         self.reverb = reverb                         # a Reverb: the bank the drawn impulse responses of a batch come from
+        self.speed = speed                           # a SpeedPerturb: the tables the drawn speed factors of a batch name
 
     def __call__(self, wavs, offsets=None):
         spec = None
@@ -74,6 +76,9 @@ class BatchSpectrogram(object):
             if wavs.reverb is not None and self.reverb is None:
                 raise RuntimeError('the batch carries reverberation draws (ToTensor(reverb=...)) but this BatchSpectrogram '
                                    'was built without an RIR bank: pass reverb=<the Reverb> to it')
+            if wavs.speed is not None and self.speed is None:
+                raise RuntimeError('the batch carries speed draws (ToTensor(speed=...)) but this BatchSpectrogram was built '
+                                   'without the tables: pass speed=<the SpeedPerturb> to it')
             spec = wavs.spec
             if spec is not None and self.spec_augment is None:
                 raise RuntimeError('the batch carries SpecAugment draws (ToTensor(spec_augment=...)) but this '
@@ -82,7 +87,10 @@ class BatchSpectrogram(object):
                 torch.cuda.current_stream().wait_event(wavs.ready)
                 wavs.pcm.record_stream(torch.cuda.current_stream())
             pcm = wavs.pcm if wavs.pcm.is_cuda else wavs.pcm.to(self.device, non_blocking=True)
-            flat, offs = ops.decode_augment(pcm, wavs.offsets, wavs.tempos, wavs.gains_db, scale=self.scale)
+            offsets = wavs.offsets
+            if wavs.speed is not None:               # speed factors drawn by the loader: the int16 clips are resampled first
+                pcm, offsets = self.speed.apply_batch(pcm, offsets, wavs.speed)
+            flat, offs = ops.decode_augment(pcm, offsets, wavs.tempos, wavs.gains_db, scale=self.scale)
             if wavs.reverb is not None:              # RIRs drawn by the loader: convolved between gain and noise
                 flat = self.reverb.apply_batch(flat, offs, wavs.reverb)
             if wavs.noise is not None:               # noise drawn by the loader: mixed in place, between gain and the STFT
@@ -126,15 +134,16 @@ class Compose(object):
 class PCMClip(object):
     """What a loader worker hands on for one utterance: the int16 samples as read from the file plus the augmentation
     DRAWN for it (tempo factor, gain in dB; None = no augmentation; ``noise``: what ``NoiseInjection.draw`` returned;
-    ``spec``: what ``SpecAugment.draw`` returned; ``reverb``: what ``Reverb.draw`` returned).  The arithmetic -- int16 ->
+    ``spec``: what ``SpecAugment.draw`` returned; ``reverb``: what ``Reverb.draw`` returned; ``speed``: what
+    ``SpeedPerturb.draw`` returned).  The arithmetic -- speed perturbation of the int16 samples, int16 ->
     float, WSOLA tempo, gain, 16-bit requantisation, reverberation, noise mixing, and behind the spectrogram the SpecAugment
-    masks -- happens on the GPU after collate (``ds2hip.ops.decode_augment``, ``ds2hip.ops.reverb``,
-    ``ds2hip.ops.noise_mix``, ``ds2hip.ops.spec_augment``)."""
-    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise', 'spec', 'reverb')
+    masks -- happens on the GPU after collate (``ds2hip.ops.resample_var``, ``ds2hip.ops.decode_augment``,
+    ``ds2hip.ops.reverb``, ``ds2hip.ops.noise_mix``, ``ds2hip.ops.spec_augment``)."""
+    __slots__ = ('pcm', 'tempo', 'gain_db', 'noise', 'spec', 'reverb', 'speed')
 
-    def __init__(self, pcm, tempo=None, gain_db=None, noise=None, spec=None, reverb=None):
+    def __init__(self, pcm, tempo=None, gain_db=None, noise=None, spec=None, reverb=None, speed=None):
         self.pcm, self.tempo, self.gain_db, self.noise, self.spec = pcm, tempo, gain_db, noise, spec
-        self.reverb = reverb
+        self.reverb, self.speed = reverb, speed
 
     def numel(self):
         return int(self.pcm.numel())
@@ -144,11 +153,12 @@ class RawAudioBatch(object):
     """A collated minibatch of ``PCMClip``s: ONE int16 buffer (page-locked when the DataLoader pins) + clip offsets +
     the per-clip augmentation parameters.  2 bytes per sample cross PCIe; everything else happens on the device.
     ``noise``: the clips' ``NoiseInjection.draw`` results (None for a clip without noise), or None when no clip drew any;
-    ``spec``: the same for ``SpecAugment.draw``; ``reverb``: the same for ``Reverb.draw``."""
+    ``spec``: the same for ``SpecAugment.draw``; ``reverb``: the same for ``Reverb.draw``; ``speed``: the same for
+    ``SpeedPerturb.draw``."""
 
-    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None, spec=None, reverb=None):
+    def __init__(self, pcm, offsets, tempos=None, gains_db=None, noise=None, spec=None, reverb=None, speed=None):
         self.pcm, self.offsets, self.tempos, self.gains_db, self.noise = pcm, list(offsets), tempos, gains_db, noise
-        self.spec, self.reverb = spec, reverb
+        self.spec, self.reverb, self.speed = spec, reverb, speed
         self.ready = None                            # event recorded behind an asynchronous upload (DevicePrefetcher)
 
     @classmethod
@@ -163,7 +173,8 @@ class RawAudioBatch(object):
         noise = [c.noise for c in clips] if any(c.noise is not None for c in clips) else None
         spec = [c.spec for c in clips] if any(c.spec is not None for c in clips) else None
         reverb = [c.reverb for c in clips] if any(c.reverb is not None for c in clips) else None
-        return cls(pcm, offs, tempos, gains, noise, spec, reverb)
+        speed = [c.speed for c in clips] if any(c.speed is not None for c in clips) else None
+        return cls(pcm, offs, tempos, gains, noise, spec, reverb, speed)
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -174,7 +185,7 @@ class RawAudioBatch(object):
 
     def to(self, device, non_blocking=False):
         out = RawAudioBatch(self.pcm.to(device, non_blocking=non_blocking), self.offsets, self.tempos, self.gains_db,
-                            self.noise, self.spec, self.reverb)
+                            self.noise, self.spec, self.reverb, self.speed)
         return out
 
 
@@ -193,7 +204,9 @@ class ToTensor(object):
     carries it to the ``BatchSpectrogram``: it needs ``defer=True`` (a waveform cannot carry a draw; in a per-clip pipeline
     the object itself stands behind ``ToSpectrogram``, where ``get_default_transforms`` puts it).  ``reverb`` (a ``Reverb``,
     default None) adds its draw BETWEEN the gain draw and the noise draw, under the same rule -- the order of the stages on
-    the device: tempo, gain, reverberation, noise, spectrogram, SpecAugment.  There is no
+    the device: tempo, gain, reverberation, noise, spectrogram, SpecAugment.  ``speed`` (a ``SpeedPerturb``, default None)
+    adds its draw IN FRONT of the tempo draw, under the same rule, and its stage runs on the int16 samples before everything
+    else: speed, tempo, gain, reverberation, noise, spectrogram, SpecAugment.  There is no
     host implementation in the product; ``oracle/audio.py`` specifies the arithmetic (sox itself is absent from the
     reference tree, so the tempo change is the published WSOLA algorithm with sox's defaults, not sox's samples).
 
@@ -208,11 +221,11 @@ class ToTensor(object):
     ``num_workers=0``."""
 
     def __init__(self, sample_rate=16000, augment=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), defer=False,
-                 device='cuda', scale=None, noise=None, spec_augment=None, reverb=None):
+                 device='cuda', scale=None, noise=None, spec_augment=None, reverb=None, speed=None):
         self.sample_rate, self.augment = sample_rate, augment
         self.tempo_range, self.gain_range = tempo_range, gain_range
         self.defer, self.device = defer, device
-        self.noise, self.reverb = noise, reverb
+        self.noise, self.reverb, self.speed = noise, reverb, speed
         if spec_augment is not None and not defer:
             raise ValueError('ToTensor(spec_augment=...) needs defer=True: the draw travels with the clip to the '
                              'BatchSpectrogram; in a per-clip pipeline put the SpecAugment behind ToSpectrogram')
@@ -232,6 +245,8 @@ class ToTensor(object):
     def __call__(self, path):
         import numpy as np
         clip = PCMClip(self._load(path))
+        if self.speed is not None:
+            clip.speed = self.speed.draw()
         if self.augment:
             clip.tempo = float(np.random.uniform(low=self.tempo_range[0], high=self.tempo_range[1]))
             clip.gain_db = float(np.random.uniform(low=self.gain_range[0], high=self.gain_range[1]))
@@ -248,8 +263,10 @@ class ToTensor(object):
                                'build the transform with defer=True (the minibatch is then decoded on the device after '
                                'collate) or use num_workers=0')
         batch = RawAudioBatch.from_clips([clip]).to(self.device)
-        wav, offs = ops.decode_augment(batch.pcm, batch.offsets, batch.tempos, batch.gains_db, self.sample_rate,
-                                       scale=self.scale)
+        pcm, offsets = batch.pcm, batch.offsets
+        if batch.speed is not None:
+            pcm, offsets = self.speed.apply_batch(pcm, offsets, batch.speed)
+        wav, offs = ops.decode_augment(pcm, offsets, batch.tempos, batch.gains_db, self.sample_rate, scale=self.scale)
         if batch.reverb is not None:
             wav = self.reverb.apply_batch(wav, offs, batch.reverb)
         if batch.noise is not None:
@@ -703,6 +720,101 @@ class Reverb(object):
             sum(self.lengths))
 
 
+class SpeedPerturb(object):
+    """Speed perturbation (Ko et al. 2015): with probability ``prob`` a clip is resampled by one of ``factors``, so that its
+    duration and its pitch move together -- a factor above 1 shortens the clip and raises its pitch.  The reference has
+    nothing of the kind (its ``tempo`` keeps the pitch), so every rule here is a decision (README "Speed perturbation");
+    nobody has measured the defaults' effect on WER in this model.
+
+    * ``factors`` are taken with three decimals and must lie in 0.5 .. 2.0; at most 15 distinct ones (a launch takes 16
+      tables and the identity takes one).  Factor f is the table ``ops.speed_design(f)``: the conversion from 16000 f Hz to
+      16000 Hz of ``ops.resample_design``, the same Kaiser filter as everywhere else.
+    * ``draw()`` -- what a loader worker calls -- returns None or the index into ``factors`` from, in this order,
+      ``np.random.binomial(1, prob)`` and then, only on a hit, ``np.random.choice(len(factors))``.
+    * a clip of n samples comes out with ``ceil(n L / M)`` samples, M / L = f reduced; int16 in, int16 out, rounded half to
+      even and saturated.  A clip without a draw (and factor 1.0) is copied bit for bit.
+
+    The arithmetic is ONE device launch for a whole minibatch, every clip with its own table, without a host wait
+    (``ds2hip.ops.resample_var``, ``ds2_resample_var``); the tables live on the GPU as one float32 bank, uploaded on first use
+    in the process that owns the GPU (never in a loader worker: the workers only draw).  ``ToTensor(speed=...)`` attaches the
+    draw to its clip and ``BatchSpectrogram(speed=...)`` resamples the int16 clips before decode, tempo and gain.
+    ``__call__(x)`` is the per-clip contract on a 1-D int16 tensor through the same kernel."""
+
+    MAX_FACTORS = ops.RESAMPLE_VAR_TABLES - 1
+
+    def __init__(self, factors=(0.9, 1.0, 1.1), prob=1.0, device='cuda'):
+        try:
+            factors = list(factors)
+        except TypeError:
+            raise ValueError('SpeedPerturb: factors must be a sequence of numbers, got %r' % (factors,))
+        if not factors:
+            raise ValueError('SpeedPerturb: factors is empty')
+        try:
+            self.factors = tuple(ops.speed_factor(f) for f in factors)
+        except ValueError as e:
+            raise ValueError('SpeedPerturb: factors: %s' % e)
+        if len(set(self.factors)) > self.MAX_FACTORS:
+            raise ValueError('SpeedPerturb: factors holds %d distinct values; at most %d (one launch takes %d tables and the '
+                             'identity takes one)' % (len(set(self.factors)), self.MAX_FACTORS, ops.RESAMPLE_VAR_TABLES))
+        if isinstance(prob, bool) or not 0.0 <= float(prob) <= 1.0:
+            raise ValueError('SpeedPerturb: prob must lie in [0, 1], got %r' % (prob,))
+        self.prob, self.device = float(prob), device
+        # table 0 is the identity (clips without a draw); every distinct factor has one table, in order of first appearance
+        self._distinct = [1.0] + [f for i, f in enumerate(self.factors) if f != 1.0 and f not in self.factors[:i]]
+        self._table_of = tuple(self._distinct.index(f) for f in self.factors)
+        self._tables = None
+
+    def __getstate__(self):                          # (a spawned loader worker gets the description, never the tables)
+        state = dict(self.__dict__)
+        state['_tables'] = None
+        return state
+
+    def draw(self, rng=None):
+        """None (this clip keeps its speed) or the index into ``factors``.  ``rng`` (a ``numpy.random.RandomState`` or
+        ``Generator``) replaces the global ``np.random`` when given."""
+        import numpy as np
+        r = np.random if rng is None else rng
+        if not r.binomial(1, self.prob):
+            return None
+        return int(r.choice(len(self.factors)))
+
+    def tables(self):
+        """The ``(L, M, taps)`` of ``ops.resample_var``: the identity, then one per distinct factor.  Designed on first use."""
+        if self._tables is None:
+            self._tables = [ops.speed_design(f) for f in self._distinct]
+        return self._tables
+
+    def table_ids(self, draws):
+        """Per-clip table index for ``ops.resample_var`` from the clips' draws (None: the identity)."""
+        return [0 if d is None else self._table_of[d] for d in draws]
+
+    def out_len(self, n, draw):
+        """Samples a clip of ``n`` samples has behind the stage."""
+        L, M, _ = self.tables()[self.table_ids([draw])[0]]
+        return ops.resample_out_len(n, L, M)
+
+    def apply_batch(self, pcm, offsets, draws):
+        """Resample the flat int16 clips on the device, one launch on the current stream, no host wait.  Returns the NEW flat
+        int16 buffer and its offsets (a python list); clips without a draw are copied."""
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError('SpeedPerturb resamples on the GPU and cannot run in a DataLoader worker process; let the '
+                               'worker draw (ToTensor(speed=..., defer=True)) and resample after collate '
+                               '(BatchSpectrogram(speed=...))')
+        return ops.resample_var(pcm, offsets, self.table_ids(draws), self.tables())
+
+    def __call__(self, x):
+        """x: 1-D int16 tensor of samples -> the clip at the drawn speed (probability ``prob``), on x's device."""
+        assert isinstance(x, torch.Tensor) and x.dim() == 1 and x.dtype == torch.int16, 'expected 1-D int16 samples'
+        draw = self.draw()
+        if draw is None or x.numel() == 0:
+            return x
+        pcm = x.to(self.device).contiguous()
+        return self.apply_batch(pcm, [0, pcm.numel()], [draw])[0].to(x.device)
+
+    def __repr__(self):
+        return '{}(factors={}, prob={})'.format(self.__class__.__name__, self.factors, self.prob)
+
+
 class SpecAugment(object):
     """SpecAugment (Park et al. 2019) on the log-spectrogram: a time warp, ``freq_masks`` frequency masks and ``time_masks``
     time masks per clip.  The reference has nothing of the kind -- its augmentation is tempo, gain and noise, all on the
@@ -824,6 +936,15 @@ def waveform_spec_augment(transform):
     for t in getattr(transform, 'transforms', [transform]):
         if isinstance(t, ToTensor):
             return t.spec_augment
+    return None
+
+
+def waveform_speed(transform):
+    """The ``SpeedPerturb`` whose draws the ``ToTensor`` stage of ``transform`` attaches to its clips (None when there is
+    none): what the ``BatchSpectrogram`` that decodes those clips must be built with."""
+    for t in getattr(transform, 'transforms', [transform]):
+        if isinstance(t, ToTensor):
+            return t.speed
     return None
 
 

@@ -3,7 +3,7 @@
 Config schema (unchanged): ``model{name, langs, freeze_layers, map_fc, params}``,
 ``training{num_epochs, batch_size, max_norm, augment, finetune}``, ``optimizer{name, params, per_layer_lr}``,
 ``scheduler{name, params}``.  Additions: ``training.audio_scale`` (``audio_scale``) and the optional block
-``training.noise{path, noise_levels, prob}`` (``get_noise``), ``training.reverb{path, prob, ...}`` (``get_reverb``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
+``training.noise{path, noise_levels, prob}`` (``get_noise``), ``training.reverb{path, prob, ...}`` (``get_reverb``), ``training.speed{factors, prob}`` (``get_speed``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
 (SURVEY.md section 4): ``langs[0]`` is the fine-tune target language, the new FC layer's *weight* is
 normally initialised.
 """
@@ -34,6 +34,9 @@ def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     ``training.reverb`` (``get_reverb``) likewise: the training ``ToTensor`` draws (``transforms.waveform_reverb(train_t)``
     is what the training ``BatchSpectrogram`` is built with), or, without ``gpu_frontend``, the ``Reverb`` stands in front
     of the ``NoiseInjection``.
+    ``training.speed`` (``get_speed``) likewise: the training ``ToTensor`` draws, in front of the tempo draw
+    (``transforms.waveform_speed(train_t)`` is what the training ``BatchSpectrogram`` is built with), and without
+    ``gpu_frontend`` the per-clip ``ToTensor`` applies it itself, before its decode.
     ``noise=False`` (evaluation: ``load_model(return_transforms=True)``) does not even look at any of these blocks."""
     augment = bool(config.training.get('augment', False))       # tempo + gain on the training set only
     # gpu_frontend: workers hand on int16 clips + the drawn (tempo, gain); decode, WSOLA, gain and the spectrogram all run
@@ -43,11 +46,12 @@ def get_default_transforms(data_dir, config, gpu_frontend=True, noise=True):
     bank = get_noise(data_dir, config, scale) if noise else None
     spec = get_spec_augment(config) if noise else None
     rir = get_reverb(data_dir, config) if noise else None
+    speed = get_speed(config) if noise else None
     if gpu_frontend:
         train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=True, scale=scale, noise=bank,
-                                                          spec_augment=spec, reverb=rir)])
+                                                          spec_augment=spec, reverb=rir, speed=speed)])
     else:
-        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=False, scale=scale)] +
+        train_t = transforms.Compose([transforms.ToTensor(augment=augment, defer=False, scale=scale, speed=speed)] +
                                      ([rir] if rir is not None else []) + ([bank] if bank is not None else []) + tail + ([spec] if spec is not None else []))
     val_t = transforms.Compose([transforms.ToTensor(augment=False, defer=gpu_frontend, scale=scale)] + tail)
     target_t = [transforms.ToLabel(os.path.join(data_dir, 'labels.{}.json'.format(lang)), lang=lang,
@@ -103,6 +107,26 @@ def get_reverb(data_dir, config):
     rir = transforms.Reverb(_resolve(block['path'], data_dir), **{k: block[k] for k in REVERB_KEYS[1:] if k in block})
     LOG.info('Reverberation on the training set: {}'.format(rir))
     return rir
+
+
+SPEED_KEYS = ('factors', 'prob')
+
+
+def get_speed(config):
+    """``training.speed`` of the JSON config (an addition to the reference's schema): ``{"factors": [0.9, 1.0, 1.1],
+    "prob": 1.0}`` -> a ``transforms.SpeedPerturb`` (None without the block).  Keys left out keep the constructor's defaults
+    (``{}`` is all defaults); an unknown key is refused by name.  Independent of ``training.augment`` and of the other blocks;
+    it reaches the training set only.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""
+    training = config.get('training', {}) if hasattr(config, 'get') else {}
+    block = (training or {}).get('speed', None)
+    if block is None:
+        return None
+    unknown = sorted(set(block) - set(SPEED_KEYS))
+    if unknown:
+        raise ValueError('training.speed: unknown key(s) %s; it takes %s' % (', '.join(unknown), ', '.join(SPEED_KEYS)))
+    speed = transforms.SpeedPerturb(**{k: block[k] for k in SPEED_KEYS if k in block})
+    LOG.info('Speed perturbation on the training set: {}'.format(speed))
+    return speed
 
 
 SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'time_warp', 'prob', 'mask_value')

@@ -37,6 +37,7 @@ SIGNATURES = {
     'ds2_reverb': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'ds2_resample_out_len': (_Z, [_Z, _I, _I]),
     'ds2_resample': (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    'ds2_resample_var': (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _Z, _I, _P, _P]),
     'ds2_spec_augment': (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _F, _P]),
     'ds2_vad_segment_ws_bytes': (_Z, [_Z]),
     'ds2_vad_segment': (_I, [_P, _Z, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _I, _P, _P]),

@@ -345,7 +345,103 @@ def resample(pcm, offsets, rate_in, rate_out=16000, channels=1, taps=None):
     return out, [int(v) for v in out_off]
 
 
-VAD_BLOCK = 160                         # DS2_VAD_BLOCK of include/ds2hip.h: samples per block of ds2_vad_segment (10 ms)
+RESAMPLE_VAR_TABLES = 16                # DS2_RESAMPLE_VAR_TABLES of include/ds2hip.h: tables of one ds2_resample_var launch
+SPEED_RANGE = (0.5, 2.0)                # factors speed_design takes
+
+
+def speed_factor(factor):
+    """A speed factor as the kernel's table is designed for it: three decimals, as the tempo draw is printed.  Outside
+    ``SPEED_RANGE`` (or not a number): ValueError naming the value."""
+    if isinstance(factor, bool) or not isinstance(factor, (int, float)) or not SPEED_RANGE[0] <= factor <= SPEED_RANGE[1]:
+        raise ValueError('speed: a factor of %r is not supported (%s .. %s)' % ((factor,) + SPEED_RANGE))
+    return float('{:.3f}'.format(factor))
+
+
+def speed_design(factor):
+    """The polyphase filter of speed perturbation by ``factor`` (taken with three decimals): ``(L, M, taps)`` of
+    ``resample_design(16 * round(1000 * factor))`` -- a conversion from 16000 * factor Hz to 16000 Hz, so M / L = factor
+    reduced, L <= 1000, and the filter, its roll-off and its cache are the existing design's.  A factor above 1 shortens the
+    clip and raises its pitch; 1.0 is the identity (one tap of 1)."""
+    return resample_design(16 * int(round(1000 * speed_factor(factor))))
+
+
+_resample_var_banks = {}
+
+
+def _resample_var_bank(tables, device):
+    """(device tap bank, (T, 4) int32 host array of {L, M, K, tap_offset}) for a list of ``(L, M, taps)``.  Cached per
+    (tables, device) when every taps array is read-only (what ``resample_design`` returns: its identity stands for its
+    contents); a writable array is uploaded per call."""
+    import numpy as np
+    if not 1 <= len(tables) <= RESAMPLE_VAR_TABLES:
+        raise ValueError('resample_var: %d tables, not 1 .. %d' % (len(tables), RESAMPLE_VAR_TABLES))
+    frozen = all(isinstance(t[2], np.ndarray) and not t[2].flags.writeable for t in tables)
+    key = (tuple((int(L), int(M), id(taps)) for L, M, taps in tables), device)
+    if frozen and key in _resample_var_banks:
+        return _resample_var_banks[key][:2]
+    desc, parts, pos = [], [], 0
+    for i, (L, M, taps) in enumerate(tables):
+        L, M = int(L), int(M)
+        table = np.ascontiguousarray(taps.cpu().numpy() if isinstance(taps, torch.Tensor) else taps)
+        if table.dtype != np.float32 or table.ndim != 2 or table.shape[0] != L:
+            raise ValueError('resample_var: table %d: taps must be an (L, K) float32 table, L = %d' % (i, L))
+        K = int(table.shape[1])
+        if not (1 <= L <= RESAMPLE_MAX_L and 1 <= M <= RESAMPLE_MAX_M and 1 <= K <= RESAMPLE_MAX_TAPS and K % 2 == 1):
+            raise ValueError('resample_var: table %d: ratio %d / %d with %d taps per phase; L in 1..%d, M in 1..%d, taps odd in '
+                             '1..%d' % (i, L, M, K, RESAMPLE_MAX_L, RESAMPLE_MAX_M, RESAMPLE_MAX_TAPS))
+        desc.append((L, M, K, pos))
+        parts.append(table.reshape(-1))
+        pos += L * K
+    bank = torch.from_numpy(np.concatenate(parts)).to(device)
+    desc = np.asarray(desc, np.int32).reshape(-1, 4)
+    if frozen:
+        _resample_var_banks[key] = (bank, desc, [t[2] for t in tables])      # (the arrays stay alive: their ids stay theirs)
+    return bank, desc
+
+
+def resample_var(pcm, offsets, table_ids, tables):
+    """Per-clip sample-rate conversion of a flat buffer of mono clips in ONE launch on the current stream, without a host
+    wait (``ds2_resample_var``): speed perturbation.  pcm: 1-D int16 on the device, clip b = pcm[offsets[b] : offsets[b + 1]];
+    offsets: python sequence (B+1); ``table_ids``: B indices into ``tables``, a list of up to 16 ``(L, M, taps)`` with taps an
+    (L, K) float32 array (``speed_design`` / ``resample_design``).  Returns ``(out, out_offsets)`` as ``resample`` does; a clip's
+    samples are bit for bit those of ``resample`` on that clip alone with its table."""
+    import numpy as np
+    if not isinstance(pcm, torch.Tensor) or not pcm.is_cuda or pcm.dtype != torch.int16 or pcm.dim() != 1:
+        raise RuntimeError('resample_var takes a 1-D int16 tensor on the device')
+    if not pcm.is_contiguous():
+        raise RuntimeError('ds2hip entry points take contiguous tensors')
+    tables = list(tables)
+    bank, desc = _resample_var_bank(tables, pcm.device)
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    ids = np.asarray(table_ids, np.int64).reshape(-1)
+    bsz = len(off) - 1
+    if not 1 <= bsz <= 65535:
+        raise ValueError('resample_var: %d clips, not 1 .. 65535' % bsz)
+    if len(ids) != bsz:
+        raise ValueError('resample_var: %d table ids for %d clips' % (len(ids), bsz))
+    if ((ids < 0) | (ids >= len(tables))).any():
+        b = int(np.argmax((ids < 0) | (ids >= len(tables))))
+        raise ValueError('resample_var: clip %d names table %d; there are %d' % (b, ids[b], len(tables)))
+    lens = np.diff(off)
+    if off[0] < 0 or (lens < 0).any() or off[-1] > pcm.numel():
+        raise ValueError('resample_var: offsets do not describe clips inside the sample buffer')
+    n_out = (lens * desc[ids, 0].astype(np.int64) + desc[ids, 1] - 1) // desc[ids, 1]
+    if n_out.max() >= 2 ** 31:
+        raise ValueError('resample_var: a clip of %d outputs; fewer than 2^31' % n_out.max())
+    out_off = np.concatenate([[0], np.cumsum(n_out)]).astype(np.int64)
+    out = torch.empty((int(out_off[-1]),), dtype=torch.int16, device=pcm.device)
+    if out_off[-1] > 0:
+        ids_pad = np.zeros(2 * ((bsz + 1) // 2), np.int32)
+        ids_pad[:bsz] = ids
+        # one upload: the two int64 offset arrays, then the int32 ids viewed as int64 pairs
+        meta_d = upload_small(torch.from_numpy(np.concatenate([off, out_off, ids_pad.view(np.int64)])), pcm.device)
+        a = bsz + 1
+        lib.call('ds2_resample_var', pcm, meta_d[:a], meta_d[a:2 * a], meta_d[2 * a:].view(torch.int32), bsz,
+                 desc.ctypes.data, len(tables), bank, int(bank.numel()), int(n_out.max()), out)
+    return out, [int(v) for v in out_off]
+
+
+VAD_BLOCK = 160                        # DS2_VAD_BLOCK of include/ds2hip.h: samples per block of ds2_vad_segment (10 ms)
 VAD_BINS = 192                          # DS2_VAD_BINS: level bins
 
 

@@ -185,6 +185,46 @@ size_t ds2_resample_out_len(size_t n_frames, int L, int M);      /* (n_frames * 
 int ds2_resample(const int16_t* pcm, const int64_t* in_offsets, int B, int channels, int L, int M, const float* taps, int K,
                  int16_t* out, const int64_t* out_offsets, void* stream);
 
+/* ------------------------------------------------------------------ speed perturbation / per-clip ratio (csrc/resample_var.hip)
+ * Resampling a training clip by 0.9 / 1.0 / 1.1 so that duration and pitch move together (Ko et al. 2015), in front of the
+ * tempo stage (speed -> tempo -> gain -> reverberation -> noise -> spectrogram -> SpecAugment).  The reference has no such
+ * stage: the factors, the filter (ds2hip/ops.py speed_design: resample_design at 16000 * factor Hz) and every rule below are
+ * decisions, and nobody has measured their effect on WER.  ONE launch for a minibatch in which every clip has its own ratio
+ * and filter table, and -- unlike ds2_resample -- NO wait on `stream`: nothing is read back.
+ *   pcm, in_offsets   clip b = pcm[in_offsets[b] .. in_offsets[b+1]), n_b mono int16 samples; (B+1) int64 on the device
+ *   out, out_offsets  clip b's outputs go to out[out_offsets[b] ..); (B+1) int64 on the device (the caller computes them
+ *                     with ds2_resample_out_len; the last entry is not read)
+ *   table_ids         (B) int32 on the device: the table of clip b
+ *   tables_host       n_tables entries {L, M, K, tap_offset} in HOST memory, 1..DS2_RESAMPLE_VAR_TABLES of them: validated
+ *                     before the launch and handed to the kernel by value (the array may be reused when the call returns).
+ *                     Table i is the (L, K) float32 table tap_bank[tap_offset .. tap_offset + L * K), laid out as
+ *                     ds2_resample's taps; bank_floats is the size of tap_bank in floats (device)
+ *   max_out           the longest clip's output count, which the caller knows: it sizes the grid
+ * Arithmetic: clip b with table (L, M, K, taps) gets exactly ds2_resample's polyphase rule at channels = 1 --
+ * n_out = ds2_resample_out_len(n_b, L, M), t = m * M in int64, i0 = t / L, p = t % L, ONE chain of fused multiply-adds in one
+ * fp32 accumulator from +0 over k = 0 .. K - 1 upwards, samples outside the clip zero by a predicate on the index (nothing
+ * outside the clip is loaded), out = (int16) clamp(rint(y), -32768, 32767), halves to even.  A clip's output bits EQUAL those
+ * of ds2_resample launched on that clip alone with the same (L, M, taps, K); they depend on nothing else -- not on B, the
+ * clip's position in the batch or in memory, the other clips or their tables, or a max_out larger than needed.
+ * L = M = K = 1, taps = [1] copies the clip bit for bit.  Elements of out outside every clip are not written; out must not
+ * overlap pcm.
+ * One kernel, no atomics, no workspace: a workgroup produces DS2_RESAMPLE_TILE consecutive outputs of one clip, as
+ * ds2_resample's; whether a clip's taps are read from LDS or through the cache is decided per table, and the dynamic LDS is
+ * sized for the largest LDS-resident table of the launch.
+ * Limits (DS2_ERR_ARG with a text outside them, and nothing is written): B in 1..65535; n_tables in 1..16; per table L in
+ * 1..1024, M in 1..4096, K odd in 1..1023, and the table inside the bank; max_out >= 0 (0: nothing is launched).
+ * The device cannot report an error, so these are defined instead: a clip whose table id is outside [0, n_tables) or whose
+ * length is negative is skipped -- nothing is written for it; outputs at or past max_out of a clip are not written.
+ * Added without a change of DS2_ABI_VERSION: one new symbol, no existing signature altered. */
+#define DS2_RESAMPLE_VAR_TABLES 16
+typedef struct ds2_resample_table {
+    int32_t L, M, K;
+    int32_t tap_offset;                                           /* in floats, into tap_bank */
+} ds2_resample_table;
+int ds2_resample_var(const int16_t* pcm, const int64_t* in_offsets, const int64_t* out_offsets, const int32_t* table_ids, int B,
+                     const ds2_resample_table* tables_host, int n_tables, const float* tap_bank, size_t bank_floats, int max_out,
+                     int16_t* out, void* stream);
+
 /* ------------------------------------------------------------------ SpecAugment
  * Time warp, frequency masks and time masks on the log-spectrogram of a minibatch, one launch, between ds2_spectrogram_fwd and
  * the model.  The reference has no such stage (its augmentation is tempo, gain and noise, all on the waveform): nothing here is

@@ -23,7 +23,7 @@ from codes.ctc import CTCLoss as warp_CTCLoss  # noqa: E402
 from codes.data import TaskCounts, split_tasks  # noqa: E402
 from codes.decoder import GreedyDecoder  # noqa: E402
 from codes.engine import create_evaluator, create_trainer  # noqa: E402
-from codes.transforms import (BatchSpectrogram, waveform_noise, waveform_reverb, waveform_scale,  # noqa: E402
+from codes.transforms import (BatchSpectrogram, waveform_noise, waveform_reverb, waveform_scale, waveform_speed,  # noqa: E402
                               waveform_spec_augment)
 from codes.utils import model_utils as mu  # noqa: E402
 from codes.utils import training_utils as tu  # noqa: E402
@@ -131,6 +131,7 @@ def main(argv=None):
         args.config = AttrDict(json.load(f))
         args.config = expand_values(args.config, **args)
     tu.check_multitask_config(args.config)
+    tu.get_speed(args.config)                        # (a bad training.speed block is refused here, when the config is loaded)
     multi = tu.is_multitask(args.config)
     out_dir = os.path.join(args.save_folder, args.config.model.name)
     os.makedirs(out_dir, exist_ok=True)
@@ -177,7 +178,8 @@ def main(argv=None):
     # (one frontend for both loaders, and for every task of a multi-task run: only training clips ever carry noise or
     # SpecAugment draws, so validation never touches the bank and is never masked)
     frontend = BatchSpectrogram(device=device, scale=waveform_scale(train_t), noise=waveform_noise(train_t),
-                                spec_augment=waveform_spec_augment(train_t), reverb=waveform_reverb(train_t))
+                                spec_augment=waveform_spec_augment(train_t), reverb=waveform_reverb(train_t),
+                                speed=waveform_speed(train_t))
     for ld in (train_loader, val_loader):            # decode + augmentation + STFT of the NEXT bin run on the prefetch stream
         if hasattr(ld, 'frontend'):
             ld.frontend = frontend
