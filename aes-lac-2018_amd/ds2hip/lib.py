@@ -95,6 +95,8 @@ SIGNATURES = {
     'ds2_ctc_align': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     'ds2_ctc_align_banded_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_align_banded': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    'ds2_ctc_keyword_search_ws_bytes': (_Z, [_I, _I]),
+    'ds2_ctc_keyword_search': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 404            # DS2_ABI_VERSION of include/ds2hip.h: the revision this table (and ops.py) is written against
@@ -103,6 +105,7 @@ _lib = None
 
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3           # DS2_ERR_* of include/ds2hip.h
 ALIGN_BAND_MIN, ALIGN_BAND_MAX = 64, 8192                   # DS2_ALIGN_BAND_* of include/ds2hip.h (ds2_ctc_align_banded)
+KWS_MAX_LEN = 64                                            # DS2_KWS_MAX_LEN of include/ds2hip.h (ds2_ctc_keyword_search)
 
 
 class Ds2Error(RuntimeError):

@@ -1103,6 +1103,37 @@ def ctc_align_banded(probs, sizes, labels, label_offsets, label_lens, max_label_
     return states, starts, ends, score
 
 
+def keyword_search(logp, sizes, labels, label_offsets, label_lens, min_score, max_hits=4, blank=0, ws=None):
+    """Where each of K keywords was said in each utterance, in one call on the current stream (``ds2_ctc_keyword_search``;
+    include/ds2hip.h has the definition).  logp (B,T,A) fp32 LOG-probabilities on the device; sizes (B,), flat labels,
+    label_offsets (K,), label_lens (K,) int32 and min_score (K,) float64 on the device.  ``ws``: a uint8 device tensor of at
+    least ``ds2_ctc_keyword_search_ws_bytes(B, T)`` bytes, or None to allocate one.  Returns the device tensors hits
+    (B,K,max_hits,2) int32 (start, end; -1 past the count), hit_score (B,K,max_hits) float64 (-inf past the count) and n_hits
+    (B,K) int32, the true count.  Nothing waits on the stream."""
+    for x in (logp, sizes, labels, label_offsets, label_lens, min_score):
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+    if logp.dtype != torch.float32 or min_score.dtype != torch.float64:
+        raise RuntimeError('keyword_search: logp must be float32 and min_score float64')
+    for x in (sizes, labels, label_offsets, label_lens):
+        if x.dtype != torch.int32:
+            raise RuntimeError('keyword_search: sizes, labels, label_offsets and label_lens must be int32')
+    bsz, t, a = logp.shape
+    k, max_hits = int(label_lens.numel()), int(max_hits)
+    if int(sizes.numel()) != bsz or int(label_offsets.numel()) != k or int(min_score.numel()) != k:
+        raise RuntimeError('keyword_search: sizes must have B entries; label_offsets, label_lens and min_score K entries')
+    if ws is None:
+        ws_bytes = lib.query('ds2_ctc_keyword_search_ws_bytes', bsz, t)
+        ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=logp.device)
+    shape = (bsz, max(k, 0), max(max_hits, 0))
+    hits = torch.empty(shape + (2,), dtype=torch.int32, device=logp.device)
+    hit_score = torch.empty(shape, dtype=torch.float64, device=logp.device)
+    n_hits = torch.empty(shape[:2], dtype=torch.int32, device=logp.device)
+    lib.call('ds2_ctc_keyword_search', logp, sizes, labels, label_offsets, label_lens, min_score, bsz, t, a, k, int(blank),
+             max_hits, ws, ws.numel() * ws.element_size(), hits, hit_score, n_hits)
+    return hits, hit_score, n_hits
+
+
 # ----------------------------------------------------------------------------- CTC
 def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_len, grad_scale=1.0,
                   zero_batch_if_inf=False):

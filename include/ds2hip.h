@@ -556,6 +556,50 @@ int ds2_ctc_align_banded(const float* probs, const int32_t* sizes, const int32_t
                          int blank, int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts,
                          int32_t* ends, double* score, void* stream);
 
+/* ------------------------------------------------------------------ keyword search (csrc/ctc_keyword.hip)
+ * Not in the reference, so every rule here is this project's decision.  For every utterance b of a batch and every one of K
+ * keywords: where was the keyword said, and how far must the model leave its own best path to have said it there.  Each
+ * (b, k) pair is independent of every other pair.
+ * logp (B,T,A): fp32 LOG-probabilities (the caller takes the log; there is no log_input switch).  sizes (B) clamped to 0..T;
+ * nothing past sizes[b] is read, padding may hold NaN.  labels / label_offsets / label_lens (K) as for ds2_ctc_align, one
+ * entry per KEYWORD.  min_score (K) float64.
+ *   emission   m[t] = max_a logp[t][a], a NaN counting as -inf;  e[t][a] = logp[t][a] - m[t], ONE fp32 subtraction;  e = -inf
+ *              where logp is NaN or -inf or the subtraction gives NaN (m[t] = -inf).  So e <= 0, a frame the model's best
+ *              path already spends on the wanted symbol costs 0, and scores of spans of different lengths are comparable.
+ *   states     S = 2 L - 1: l1, blank, l2, ..., lL; state s is a label if s is even and a blank if s is odd.  An occurrence
+ *              starts in l1's state and ends in lL's, so its span is tight.
+ *   recursion  in fp64, v[-1][.] = -inf, st[-1][.] = -1.  s >= 1: v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if s is
+ *              even and ext[s] != ext[s-2]) + e[t][ext[s]];  s = 0: v[t][0] = max(v[t-1][0], 0) + e[t][l1], the 0 being a
+ *              fresh start at frame t.  st[t][s], the start frame of the state's best path, is copied from the chosen
+ *              predecessor and is t on a fresh start.  Ties: stay, then s-1, then s-2 (strict > in that order); at state 0
+ *              stay wins over a fresh start, so a run of zero-cost first-label frames starts at its first frame.
+ *              D[t] = v[t][S-1] with st[t][S-1] is the best occurrence ending at t.  No back-trace, no per-frame workspace.
+ *   hits       the candidate (D[t], st[t][S-1], t) counts when D[t] >= min_score[k] (a NaN threshold compares false).  One
+ *              streaming pass over t clusters them: with no current hit the candidate becomes it; if the candidate's start
+ *              lies after the current hit's end, the current hit is emitted and the candidate becomes current; otherwise
+ *              the candidate replaces the current hit if its score is greater, or equal with the same start (which extends
+ *              the end across a plateau); any other candidate is dropped.  The current hit is emitted after the last frame.
+ *              Hits come out with ascending ends; a hit MAY BEGIN BEFORE THE PREVIOUS ONE ENDS (a better candidate
+ *              replaces the current hit whatever its start, and only the FIRST candidate of a cluster was held against the
+ *              emitted hit's end).
+ * Outputs: hits (B,K,max_hits,2) int32 (start, end) inclusive, -1 past the count; hit_score (B,K,max_hits) float64, -inf past
+ * the count; n_hits (B,K) int32 the TRUE count, which may exceed max_hits: the first max_hits are then written and nothing
+ * past them is touched.
+ * 1 <= L <= DS2_KWS_MAX_LEN; a keyword outside that range, or with a label outside [0, A) or equal to blank, has n_hits = 0
+ * for every utterance (checked on the device).  DS2_ERR_ARG before any launch: A outside 1..256; K outside 1..65535;
+ * max_hits outside 1..64; blank outside [0, A); B or T negative or B T > 2^25; a NULL pointer; a workspace smaller than
+ * ds2_ctc_keyword_search_ws_bytes(B, T) (the message names the needed size).  The workspace holds m, need not be zeroed and
+ * is written only below sizes[b].
+ * Results are bit-identical from run to run and depend neither on the batch's other utterances, nor on the other keywords,
+ * nor on the workspace's contents.  Two launches on the stream (row maxima, search); no workgroup waits on another.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_KWS_MAX_LEN 64
+size_t ds2_ctc_keyword_search_ws_bytes(int B, int T);
+int ds2_ctc_keyword_search(const float* logp, const int32_t* sizes, const int32_t* labels, const int32_t* label_offsets,
+                           const int32_t* label_lens, const double* min_score, int B, int T, int A, int K, int blank,
+                           int max_hits, void* ws, size_t ws_bytes, int32_t* hits, double* hit_score, int32_t* n_hits,
+                           void* stream);
+
 /* ------------------------------------------------------------------ voice-activity segmentation (csrc/vad.hip)
  * Not in the reference (it cuts its corpora with dataset scripts and sox).  Cuts a recording of any length into the clips the
  * model was trained on, from the int16 samples already on the device.  Integer arithmetic only: a result is exact.
