@@ -88,6 +88,20 @@ class GreedyDecoder(Decoder):
         offsets = [[torch.IntTensor(offs[b, :lens[b]].copy())] for b in range(bsz)]
         return strings, offsets
 
+    def decode_labels(self, probs, sizes=None):
+        """``decode`` without the trip to the host: (labels (B,T) int32, lens (B,) int32) on the device, row b holding the
+        label ids of ``decode``'s string b -- the layout ``ops.edit_stats`` scores.  Nothing waits on the stream."""
+        if not probs.is_cuda:
+            raise RuntimeError('GreedyDecoder.decode_labels runs on device tensors only')
+        bsz, t, a = probs.shape
+        best = ops.argmax_rows(probs.contiguous().float().view(bsz * t, a), bsz * t, a).view(bsz, t)
+        if sizes is None:
+            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
+        else:
+            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32)
+        ids, _, lens = ops.greedy_collapse(best, sizes_d, self.blank_index)
+        return ids, lens
+
 
 class BeamCTCDecoder(GreedyDecoder):
     """CTC prefix beam search without a language model (not in the reference).
@@ -160,3 +174,19 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         strings = [[self._to_string(labels[b, :lens[b]])] for b in range(bsz)]
         offsets = [[torch.IntTensor(offs[b, :lens[b]].copy())] for b in range(bsz)]
         return strings, offsets
+
+    def decode_labels(self, probs, sizes=None):
+        """``decode`` without the trip to the host: (labels (B,T) int32, lens (B,) int32) on the device, row b holding the
+        label ids of ``decode``'s string b -- the layout ``ops.edit_stats`` scores.  Nothing waits on the stream, and
+        ``last_scores`` / ``last_ctc_log_probs`` are left as they were."""
+        if not probs.is_cuda:
+            raise RuntimeError('DeviceBeamCTCDecoder.decode_labels runs on device tensors only')
+        bsz, t, _ = probs.shape
+        if sizes is None:
+            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
+        else:
+            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+        labels, _, lens, _, _ = ops.ctc_beam_search(
+            probs.detach().contiguous().float(), sizes_d, self.beam_width, self.blank_index, self.log_input, self.lm,
+            self.alpha, self.beta, self.space_id)
+        return labels, lens

@@ -1,4 +1,6 @@
-// Batched CTC prefix beam search on the device, with optional n-gram LM shallow fusion (ds2_ctc_beam_search_batch).
+// Batched CTC prefix beam search on the device, with optional n-gram LM shallow fusion (ds2_ctc_beam_search_batch), and the
+// same search with the output rows decoupled from the utterances, each row with its own LM weights (ds2_ctc_beam_search_rows:
+// many (alpha, beta) pairs over one batch in one launch; DESIGN.md "LM weight tuning").
 // Not in the reference (its test.py offers greedy / none); the host search ds2_ctc_beam_search (decode_host.hip) is the
 // no-LM yardstick and tests/beam_ref.py the pure-Python statement of the contract.  DESIGN.md "Device CTC beam search".
 //
@@ -185,16 +187,42 @@ __device__ inline void stay_scores(const BeamLds& s, int i, int blank, double* n
     *npnb = q;
 }
 
+// ROWS = false: workgroup b decodes utterance b with the weights in lm_in (ds2_ctc_beam_search_batch).
+// ROWS = true: workgroup r decodes utterance utt[r] with alpha_r[r] / beta_r[r] into output row r and node array r
+// (ds2_ctc_beam_search_rows); everything after these first lines is the same code for both.
+template <bool ROWS>
 __global__ void __launch_bounds__(BEAM_THREADS)
-ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ sizes, int T, int A, int blank, int W,
-                int log_input, LmArgs lm, BeamNode* __restrict__ nodes_all, int32_t* __restrict__ out_labels,
+ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ sizes, int B, int T, int A, int blank, int W,
+                int log_input, LmArgs lm_in, const int32_t* __restrict__ utt, const float* __restrict__ alpha_r,
+                const float* __restrict__ beta_r, BeamNode* __restrict__ nodes_all, int32_t* __restrict__ out_labels,
                 int32_t* __restrict__ out_offsets, int32_t* __restrict__ out_len, float* __restrict__ out_score,
                 float* __restrict__ out_ctc) {
     extern __shared__ __attribute__((aligned(16))) uint64_t keys[];   // W * A candidate keys
     __shared__ BeamLds s;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = min(max(sizes[b], 0), T);
-    const float* pr = probs + (size_t)b * T * A;
+    const int b = blockIdx.x, tid = threadIdx.x;      // b: the output row (and the node array); u: the utterance it decodes
+    int u = b;
+    LmArgs lm = lm_in;
+    if (ROWS) {
+        u = utt[b];
+        if (u < 0 || u >= B) {      // no utterance: the empty labelling at -inf, nothing of probs or sizes is read
+            if (tid == 0) {
+                out_len[b] = 0;
+                out_score[b] = (float)NEG_INF;
+                out_ctc[b] = (float)NEG_INF;
+            }
+            for (int q = tid; q < T; q += BEAM_THREADS) {
+                out_labels[(size_t)b * T + q] = 0;
+                out_offsets[(size_t)b * T + q] = 0;
+            }
+            return;
+        }
+        if (lm.unit) {              // float -> double once, as the batch entry converts its two scalars
+            lm.alpha = (double)alpha_r[b];
+            lm.beta = (double)beta_r[b];
+        }
+    }
+    const int n = min(max(sizes[u], 0), T);
+    const float* pr = probs + (size_t)u * T * A;
     BeamNode* nodes = nodes_all + (size_t)b * (1 + (size_t)T * W);
     const int NC = W * A;
     const int chunk = (NC + BEAM_THREADS - 1) / BEAM_THREADS;   // contiguous candidate range per thread (scans)
@@ -450,36 +478,47 @@ extern "C" size_t ds2_ctc_beam_ws_bytes(int B, int T, int W) {
     return (size_t)B * (1 + (size_t)T * W) * sizeof(BeamNode);
 }
 
-extern "C" int ds2_ctc_beam_search_batch(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
-                                         int beam_width, int log_input, const void* ngram_table, int ngram_cap,
-                                         const void* word_table, int word_cap, int order, int unit, int bos_id,
-                                         int eos_id, int unk_id, int space_id, float alpha, float beta, float oov_logp,
-                                         void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets,
-                                         int32_t* out_len, float* out_score, float* out_ctc_logp, void* stream) {
+namespace {
+
+#define BEAM_CHECK_ARG(cond)                                          \
+    do {                                                              \
+        if (!(cond)) {                                                \
+            ds2_set_error("%s: bad argument: %s", fn, #cond);         \
+            return DS2_ERR_ARG;                                       \
+        }                                                             \
+    } while (0)
+
+// the checks and the launch both entries share; R workgroups, utt == nullptr for the batch entry (R == B)
+int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B, int R, int T, int A, int blank,
+                int beam_width, int log_input, const void* ngram_table, int ngram_cap, const void* word_table, int word_cap,
+                int order, int unit, int bos_id, int eos_id, int unk_id, int space_id, float alpha, float beta,
+                float oov_logp, const int32_t* utt, const float* alpha_r, const float* beta_r, void* ws, size_t ws_bytes,
+                int32_t* out_labels, int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
+                void* stream) {
     if (beam_width < 1 || beam_width > MAX_W) {
-        ds2_set_error("ds2_ctc_beam_search_batch: beam_width %d is outside 1..%d", beam_width, MAX_W);
+        ds2_set_error("%s: beam_width %d is outside 1..%d", fn, beam_width, MAX_W);
         return DS2_ERR_ARG;
     }
     if (A < 1 || A > MAX_A) {
-        ds2_set_error("ds2_ctc_beam_search_batch: alphabet size %d is outside 1..%d", A, MAX_A);
+        ds2_set_error("%s: alphabet size %d is outside 1..%d", fn, A, MAX_A);
         return DS2_ERR_ARG;
     }
-    DS2_CHECK_ARG(B >= 0 && T >= 0 && blank >= 0 && blank < A && unit >= 0 && unit <= 2);
-    DS2_CHECK_ARG(sizes && out_labels && out_offsets && out_len && out_score && out_ctc_logp && (probs || T == 0 || B == 0));
+    BEAM_CHECK_ARG(B >= 0 && R >= 0 && T >= 0 && blank >= 0 && blank < A && unit >= 0 && unit <= 2);
+    BEAM_CHECK_ARG(sizes && out_labels && out_offsets && out_len && out_score && out_ctc_logp && (probs || T == 0 || B == 0));
     if (unit) {
         if (order < 1 || order > MAX_ORDER) {
-            ds2_set_error("ds2_ctc_beam_search_batch: LM order %d is outside 1..%d", order, MAX_ORDER);
+            ds2_set_error("%s: LM order %d is outside 1..%d", fn, order, MAX_ORDER);
             return DS2_ERR_ARG;
         }
-        DS2_CHECK_ARG(ngram_table && ngram_cap >= 2 && (ngram_cap & (ngram_cap - 1)) == 0);
-        DS2_CHECK_ARG(unit == 1 || (word_table && word_cap >= 2 && (word_cap & (word_cap - 1)) == 0 && space_id < A));
+        BEAM_CHECK_ARG(ngram_table && ngram_cap >= 2 && (ngram_cap & (ngram_cap - 1)) == 0);
+        BEAM_CHECK_ARG(unit == 1 || (word_table && word_cap >= 2 && (word_cap & (word_cap - 1)) == 0 && space_id < A));
     }
-    if (ws_bytes < ds2_ctc_beam_ws_bytes(B, T, beam_width) || (!ws && B > 0)) {
-        ds2_set_error("ds2_ctc_beam_search_batch: workspace of %zu bytes < ds2_ctc_beam_ws_bytes = %zu", ws_bytes,
-                      ds2_ctc_beam_ws_bytes(B, T, beam_width));
+    if (ws_bytes < ds2_ctc_beam_ws_bytes(R, T, beam_width) || (!ws && R > 0)) {
+        ds2_set_error("%s: workspace of %zu bytes < ds2_ctc_beam_ws_bytes = %zu", fn, ws_bytes,
+                      ds2_ctc_beam_ws_bytes(R, T, beam_width));
         return DS2_ERR_ARG;
     }
-    if (B == 0) return DS2_OK;
+    if (R == 0) return DS2_OK;
     LmArgs lm{};
     lm.ngram = (const uint64_t*)ngram_table;
     lm.words = (const uint64_t*)word_table;
@@ -495,15 +534,60 @@ extern "C" int ds2_ctc_beam_search_batch(const float* probs, const int32_t* size
     lm.beta = unit ? (double)beta : 0.0;
     lm.oov = (double)oov_logp;
     const size_t dyn = (size_t)beam_width * A * sizeof(uint64_t);
+    const void* kern = utt ? reinterpret_cast<const void*>(&ctc_beam_kernel<true>)
+                           : reinterpret_cast<const void*>(&ctc_beam_kernel<false>);
     if (dyn + sizeof(BeamLds) > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)dyn) != hipSuccess) {
-        ds2_set_error("ds2_ctc_beam_search_batch: %zu bytes of LDS are not available", dyn + sizeof(BeamLds));
+        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+        ds2_set_error("%s: %zu bytes of LDS are not available", fn, dyn + sizeof(BeamLds));
         return DS2_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes, T, A, blank,
-                       beam_width, log_input, lm, (BeamNode*)ws, out_labels, out_offsets, out_len, out_score,
-                       out_ctc_logp);
-    DS2_CHECK_LAUNCH();
+    if (utt)
+        hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes, B, T,
+                           A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp);
+    else
+        hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes, B, T,
+                           A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) {
+        ds2_set_error("%s: launch failed: %s", fn, hipGetErrorString(e_));
+        return DS2_ERR_LAUNCH;
+    }
     return DS2_OK;
+}
+
+}  // namespace
+
+extern "C" int ds2_ctc_beam_search_batch(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                                         int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                                         const void* word_table, int word_cap, int order, int unit, int bos_id,
+                                         int eos_id, int unk_id, int space_id, float alpha, float beta, float oov_logp,
+                                         void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets,
+                                         int32_t* out_len, float* out_score, float* out_ctc_logp, void* stream) {
+    return beam_launch("ds2_ctc_beam_search_batch", probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table,
+                       ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp,
+                       nullptr, nullptr, nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp,
+                       stream);
+}
+
+extern "C" int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes, const int32_t* utt, const float* alpha,
+                                        const float* beta, int B, int R, int T, int A, int blank, int beam_width,
+                                        int log_input, const void* ngram_table, int ngram_cap, const void* word_table,
+                                        int word_cap, int order, int unit, int bos_id, int eos_id, int unk_id, int space_id,
+                                        float oov_logp, void* ws, size_t ws_bytes, int32_t* out_labels,
+                                        int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
+                                        void* stream) {
+    if (R < 0) {
+        ds2_set_error("ds2_ctc_beam_search_rows: %d rows", R);
+        return DS2_ERR_ARG;
+    }
+    if (R == 0) return DS2_OK;       // no rows: nothing to check, nothing is launched
+    if (!utt || (unit && (!alpha || !beta))) {
+        ds2_set_error("ds2_ctc_beam_search_rows: utt%s must not be NULL", unit ? ", alpha and beta" : "");
+        return DS2_ERR_ARG;
+    }
+    return beam_launch("ds2_ctc_beam_search_rows", probs, sizes, B, R, T, A, blank, beam_width, log_input, ngram_table,
+                       ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, 0.f, 0.f, oov_logp, utt,
+                       alpha, beta, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream);
 }

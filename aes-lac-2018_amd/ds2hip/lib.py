@@ -91,6 +91,10 @@ SIGNATURES = {
     'ds2_ctc_beam_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_beam_search_batch': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F,
                                        _P, _Z, _P, _P, _P, _P, _P, _P]),
+    'ds2_ctc_beam_search_rows': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F,
+                                      _P, _Z, _P, _P, _P, _P, _P, _P]),
+    'ds2_edit_stats_ws_bytes': (_Z, [_I, _I, _I]),
+    'ds2_edit_stats': (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _Z, _P, _P, _P]),
     'ds2_ctc_align_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_align': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     'ds2_ctc_align_banded_ws_bytes': (_Z, [_I, _I, _I]),
@@ -106,6 +110,7 @@ _lib = None
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3           # DS2_ERR_* of include/ds2hip.h
 ALIGN_BAND_MIN, ALIGN_BAND_MAX = 64, 8192                   # DS2_ALIGN_BAND_* of include/ds2hip.h (ds2_ctc_align_banded)
 KWS_MAX_LEN = 64                                            # DS2_KWS_MAX_LEN of include/ds2hip.h (ds2_ctc_keyword_search)
+EDIT_MAX_ITEMS = 2048                                       # DS2_EDIT_MAX_ITEMS of include/ds2hip.h (ds2_edit_stats)
 
 
 class Ds2Error(RuntimeError):

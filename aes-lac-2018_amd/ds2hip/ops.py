@@ -1058,6 +1058,93 @@ def ctc_beam_search(probs, sizes, beam_width, blank=0, log_input=False, lm=None,
     return labels, offsets, lens, score, ctc
 
 
+def _require_device(name, dtype, **tensors):
+    for key, x in tensors.items():
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+        if x.dtype != dtype:
+            raise RuntimeError('%s: %s must be %s, got %s' % (name, key, dtype, x.dtype))
+
+
+def ctc_beam_search_rows(probs, sizes, utt, alpha, beta, beam_width, blank=0, log_input=False, lm=None, space_id=-1):
+    """``ctc_beam_search`` with R output rows decoupled from the B utterances (``ds2_ctc_beam_search_rows``): row r decodes
+    utterance utt[r] with the LM weights alpha[r], beta[r], all rows in one launch on the current stream.  probs (B,T,A)
+    fp32 and sizes (B,) int32 on the device; utt (R,) int32, alpha, beta (R,) fp32 on the device (the weights are ignored
+    without an ``lm``).  Returns the device tensors labels (R,T), offsets (R,T), lens (R,) int32 and score, ctc_logp (R,)
+    fp32, row r bit-identical to ``ctc_beam_search`` of that utterance with those weights; a utt[r] outside [0, B) gives
+    the empty labelling at -inf.  Nothing waits on the stream."""
+    _require_device('ctc_beam_search_rows', torch.float32, probs=probs, alpha=alpha, beta=beta)
+    _require_device('ctc_beam_search_rows', torch.int32, sizes=sizes, utt=utt)
+    bsz, t, a = probs.shape
+    rows = int(utt.numel())
+    if int(sizes.numel()) != bsz or int(alpha.numel()) != rows or int(beta.numel()) != rows:
+        raise RuntimeError('ctc_beam_search_rows: sizes must have B entries; alpha and beta one per entry of utt')
+    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', rows, t, beam_width)
+    ws = _bytes_ws(ws_bytes, probs)
+    labels = torch.empty((rows, t), dtype=torch.int32, device=probs.device)
+    offsets = torch.empty((rows, t), dtype=torch.int32, device=probs.device)
+    lens = torch.empty((rows,), dtype=torch.int32, device=probs.device)
+    score = _empty((rows,), probs)
+    ctc = _empty((rows,), probs)
+    if lm is None:
+        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0)
+    else:
+        tabs = lm.to(probs.device)
+        word = tabs.get('word')
+        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
+                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(lm.oov_logp))
+    lib.call('ds2_ctc_beam_search_rows', probs, sizes, utt, alpha, beta, bsz, rows, t, a, int(blank), int(beam_width),
+             int(bool(log_input)), *lm_args, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc)
+    return labels, offsets, lens, score, ctc
+
+
+EDIT_MAX_ITEMS = lib.EDIT_MAX_ITEMS     # DS2_EDIT_MAX_ITEMS of include/ds2hip.h: labels per side ds2_edit_stats takes
+EDIT_THREADS = 256                      # DS2_EDIT_THREADS: threads of its one workgroup per (row, level)
+EDIT_CHUNK = 8                          # DS2_EDIT_CHUNK: consecutive labels a thread owns in the item pass
+EDIT_FIELDS = ('char_dist', 'char_sub', 'char_del', 'char_ins', 'ref_chars',
+               'word_dist', 'word_sub', 'word_del', 'word_ins', 'ref_words')
+
+
+def edit_stats(hyp, hyp_len, ref, ref_offsets, ref_lens, max_ref_len, space_id=-1, ref_index=None, group=None,
+               totals=None, ws=None):
+    """Word and character error counts of R label rows against their references in one launch on the current stream
+    (``ds2_edit_stats``; include/ds2hip.h has the definition).  hyp (R,stride) and hyp_len (R,) int32 on the device, as the
+    beam search and ``greedy_collapse`` return them; flat ref, ref_offsets (N,), ref_lens (N,) int32 on the device;
+    ``ref_index`` (R,) int32 picks each row's reference (None: row r uses reference r).  ``group`` (R,) int32 with
+    ``totals`` (G,10) int64: the valid rows' ten values are ADDED to totals[group[r]].  Returns stats (R,10) int32 in the
+    order of ``EDIT_FIELDS``; an invalid row is all -1.  Nothing waits on the stream."""
+    ints = dict(hyp=hyp, hyp_len=hyp_len, ref=ref, ref_offsets=ref_offsets, ref_lens=ref_lens)
+    if ref_index is not None:
+        ints['ref_index'] = ref_index
+    if group is not None:
+        ints['group'] = group
+    _require_device('edit_stats', torch.int32, **ints)
+    if hyp.dim() != 2:
+        raise RuntimeError('edit_stats: hyp must be (R, stride)')
+    rows, stride = hyp.shape
+    n_ref = int(ref_lens.numel())
+    if int(hyp_len.numel()) != rows or int(ref_offsets.numel()) != n_ref:
+        raise RuntimeError('edit_stats: hyp_len must have R entries; ref_offsets one per entry of ref_lens')
+    for x in (ref_index, group):
+        if x is not None and int(x.numel()) != rows:
+            raise RuntimeError('edit_stats: ref_index and group must have R entries')
+    n_groups = 0
+    if group is not None:
+        if totals is None:
+            raise RuntimeError('edit_stats: group needs totals (G,10) int64')
+        _require_device('edit_stats', torch.int64, totals=totals)
+        if totals.dim() != 2 or totals.shape[1] != 10 or not totals.is_contiguous():
+            raise RuntimeError('edit_stats: totals must be a contiguous (G,10) tensor')
+        n_groups = int(totals.shape[0])
+    if ws is None:
+        ws_bytes = lib.query('ds2_edit_stats_ws_bytes', rows, stride, int(max_ref_len))
+        ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=hyp.device)
+    stats = torch.empty((rows, 10), dtype=torch.int32, device=hyp.device)
+    lib.call('ds2_edit_stats', hyp, hyp_len, rows, stride, ref, ref_offsets, ref_lens, n_ref, int(max_ref_len), ref_index,
+             group, n_groups, int(space_id), ws, ws.numel() * ws.element_size(), stats, totals if group is not None else None)
+    return stats
+
+
 def ctc_align(probs, sizes, labels, label_offsets, label_lens, max_label_len, blank=0, log_input=False):
     """CTC forced alignment of a batch in one launch on the current stream (``ds2_ctc_align``).  probs (B,T,A) fp32 on the
     device; sizes (B,), flat labels, label_offsets (B,), label_lens (B,) int32 on the device.  Returns the device tensors

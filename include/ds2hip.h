@@ -505,6 +505,63 @@ int ds2_ctc_beam_search_batch(const float* probs, const int32_t* sizes, int B, i
                               size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
                               float* out_score, float* out_ctc_logp, void* stream);
 
+/* ds2_ctc_beam_search_rows: the batch search with R output rows decoupled from the B utterances, for sweeps over the LM
+ * weights: many (alpha, beta) pairs over the same probabilities in ONE launch (one workgroup per row).  Row r decodes
+ * utterance utt[r] (R int32 on the device) with alpha[r] / beta[r] (R float32 on the device; not read when unit = 0) into
+ * row r of out_labels / out_offsets (R,T) and out_len / out_score / out_ctc_logp (R).  Every other argument is as for
+ * ds2_ctc_beam_search_batch; ws >= ds2_ctc_beam_ws_bytes(R, T, beam_width).
+ * Row r equals, bit for bit, what ds2_ctc_beam_search_batch writes for utterance utt[r] with (alpha[r], beta[r]) -- labels,
+ * offsets, length, both scores and the zeros past the length (each float weight becomes a double once, as there) -- and
+ * does not depend on which other rows share the launch.  A utt[r] outside [0, B) is checked on the device: that row is the
+ * empty labelling with out_score = out_ctc_logp = -inf, and nothing of probs or sizes is read for it.
+ * R = 0 is DS2_OK; a bad size or a NULL pointer is DS2_ERR_ARG with a message, as for the batch entry.
+ * Added without a change of DS2_ABI_VERSION: one new symbol, no existing signature altered. */
+int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes, const int32_t* utt, const float* alpha,
+                             const float* beta, int B, int R, int T, int A, int blank, int beam_width, int log_input,
+                             const void* ngram_table, int ngram_cap, const void* word_table, int word_cap, int order,
+                             int unit, int bos_id, int eos_id, int unk_id, int space_id, float oov_logp, void* ws,
+                             size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
+                             float* out_score, float* out_ctc_logp, void* stream);
+
+/* ------------------------------------------------------------------ error counts from labels (csrc/edit_stats.hip)
+ * Not in the reference (its test.py makes strings and calls python-Levenshtein per utterance).  Word and character error
+ * counts of R hypothesis rows against their references in one launch, from label ids; no strings.
+ * hyp (R, hyp_stride) int32 and hyp_len (R): the layout ds2_ctc_beam_search_batch / _rows and ds2_greedy_collapse write;
+ * nothing past hyp_len[r] is read.  References as for ds2_ctc_loss_grad: flat ref, ref_offsets (N), ref_lens (N), every
+ * length <= max_ref_len.  Row r is scored against reference ref_index[r] (R int32), or against reference r if ref_index
+ * is NULL.  group (R) int32 in [0, G), or NULL for no totals.  space_id: the space label, -1 = the alphabet has none
+ * (labels are >= 0).
+ *   items     character level: the sequence with every space_id label removed (Decoder.cer).  Word level: the maximal
+ *             runs of non-space labels (str.split(): leading, trailing and repeated spaces make no word); two words are
+ *             equal only if they have the same length and the same labels (a hash filters, the labels decide).
+ *   distance  unit-cost Levenshtein over hypothesis prefix i and reference prefix j: cell (i, j), 0 <= i <= m, 0 <= j <= n.
+ *   counts    every cell takes ONE predecessor and carries that predecessor's (S, D, I) plus its own operation.  Cell
+ *             (0, 0) is (0, 0, 0); row i = 0 is all deletions, (0, j) = j D; column j = 0 is all insertions, (i, 0) = i I.
+ *             Otherwise, if hypothesis item i equals reference item j the cell takes (i-1, j-1) unchanged (a match, which
+ *             is always among the cheapest moves); if not, it takes the cheapest of substitution ((i-1, j-1) + S),
+ *             deletion (a reference item without a hypothesis item: (i, j-1) + D) and insertion ((i-1, j) + I), a tie
+ *             going to substitution, then deletion, then insertion.  The rule is per cell, so the counts of cell (m, n)
+ *             are those of a back-trace from (m, n) under the same rule; no back-pointer is stored.  S + D + I = dist.
+ * Outputs: stats (R, 10) int32 = [char_dist, char_sub, char_del, char_ins, ref_chars, word_dist, word_sub, word_del,
+ * word_ins, ref_words], ref_chars the reference's non-space labels and ref_words its words.  With group, the ten values of
+ * every valid row are ADDED to row group[r] of totals (G, 10) int64: the caller zeroes it (or keeps accumulating); the adds
+ * are integer, so the sums do not depend on their order.
+ * hyp_stride and max_ref_len <= DS2_EDIT_MAX_ITEMS, else DS2_ERR_ARG.  Checked on the device: a hyp_len[r] outside
+ * [0, hyp_stride], a reference index outside [0, N), a ref_lens outside [0, max_ref_len], a group[r] outside [0, G); such
+ * a row has -1 in all ten stats and adds nothing to the totals.
+ * ds2_edit_stats_ws_bytes(R, hyp_stride, max_ref_len) sizes ws (today 0: the table sweep lives in LDS; ws may then be
+ * NULL); its contents never matter.  One workgroup of DS2_EDIT_THREADS threads per (row, level); in the item pass a thread
+ * owns DS2_EDIT_CHUNK consecutive labels.  Results are bit-identical from run to run and do not depend on the other rows.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_EDIT_MAX_ITEMS 2048
+#define DS2_EDIT_THREADS 256
+#define DS2_EDIT_CHUNK (DS2_EDIT_MAX_ITEMS / DS2_EDIT_THREADS)
+size_t ds2_edit_stats_ws_bytes(int R, int hyp_stride, int max_ref_len);
+int ds2_edit_stats(const int32_t* hyp, const int32_t* hyp_len, int R, int hyp_stride, const int32_t* ref,
+                   const int32_t* ref_offsets, const int32_t* ref_lens, int N, int max_ref_len, const int32_t* ref_index,
+                   const int32_t* group, int G, int space_id, void* ws, size_t ws_bytes, int32_t* stats, int64_t* totals,
+                   void* stream);
+
 /* ------------------------------------------------------------------ CTC forced alignment (csrc/ctc_align.hip)
  * Not in the reference.  One launch finds, for every utterance of a batch, the single best alignment (max-sum / Viterbi) of
  * its KNOWN transcript to frames 0 .. sizes[b]-1, over the extended sequence blank, l1, blank, ..., lL, blank (state s:
