@@ -381,7 +381,11 @@ __global__ __launch_bounds__(256) void bn1d_bwd_apply_kernel(const float* __rest
 
 // ---- 16-byte forms of the three sequence-flavour kernels (F % 4 == 0, 16-byte aligned rows): the scalar forms above move
 // 4 bytes per lane and pay an integer modulo per element -- 0.8 TB/s on (4050 x 800) tensors; these read and write whole
-// float4 columns quads.  Per column the rows are summed in exactly the same order, so results are bit-identical.
+// float4 columns quads.  Per column the rows are summed in exactly the same order, with the same operations -- but the
+// results are NOT bit-identical: the compiler fuses a product into the sum that follows it in one form and not in the other
+// (here v_pk_fma_f32 on the quads, and a v_mul_f32 followed by a v_pk_add_f32 over the two accumulators in the scalar
+// forms), so sums, mean_invstd and dx differ in the last bits.  Both forms are held to float64 under the same bounds
+// (tests/test_bn_edges_gpu.py).
 template <int MODE>
 __global__ __launch_bounds__(256) void bn1d_reduce_vec_kernel(const f32x4* __restrict__ xa, const f32x4* __restrict__ xb,
                                                               const f32x4* __restrict__ dy,
@@ -481,6 +485,8 @@ extern "C" int ds2_bn2d_stats(const float* x, int B, int C, int inner, float eps
                               float* running_mean, float* running_var, float* mean_invstd, void* ws, void* stream) {
     DS2_CHECK_ARG(x && mean_invstd && ws && B > 0 && C > 0 && inner > 0);
     DS2_CHECK_ARG(!use_running || (running_mean && running_var));
+    DS2_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
+    DS2_CHECK_ARG(C <= 65535);      // grid.y of the reduction
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)ws;
     if (!use_running) {
@@ -506,6 +512,7 @@ extern "C" int ds2_bn2d_apply_htanh(const float* x, const float* mean_invstd, co
         dim3 grid(ds2_cdiv(T, 32), ds2_cdiv(C * D, 32), B);
         hipLaunchKernelGGL(bn2d_apply_tbf_kernel, grid, dim3(256), 0, st, x, mean_invstd, gamma, beta, B, C, D, T, y);
     } else {
+        DS2_CHECK_ARG((long long)B * C <= 65535);      // grid.y of both elementwise forms
         const int inner = D * T;
         if (aligned16(x) && aligned16(y)) {
             dim3 grid(min(ds2_cdiv(inner, 1024), 64), B * C);
@@ -524,6 +531,7 @@ extern "C" int ds2_bn2d_htanh_bwd(const float* x, const float* dy, const float* 
                                   float* dbeta, void* ws, void* stream) {
     DS2_CHECK_ARG(x && dy && mean_invstd && gamma && beta && dx && dgamma && dbeta && ws);
     DS2_CHECK_ARG(B > 0 && C > 0 && D > 0 && T > 0);
+    DS2_CHECK_ARG((long long)B * C <= 65535);      // grid.y of the elementwise kernel (and C of the reduction)
     hipStream_t st = (hipStream_t)stream;
     const int inner = D * T;
     double* part = (double*)ws;
@@ -555,6 +563,7 @@ extern "C" int ds2_bn1d_stats(const float* xa, const float* xb, int rows, int F,
                               void* stream) {
     DS2_CHECK_ARG(xa && mean_invstd && ws && rows > 0 && F > 0);
     DS2_CHECK_ARG(!use_running || (running_mean && running_var));
+    DS2_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)ws;
     if (!use_running) {

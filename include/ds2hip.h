@@ -333,6 +333,10 @@ int ds2_conv_wgrad(int which, const float* in, const float* d_out, int B, int t_
  * after finalisation) and updates running_mean/var; *_apply normalises.  Eval: pass
  * use_running=1 to *_stats to derive mean/invstd from the running buffers instead.
  * ws: >= ds2_bn_ws_bytes(C) bytes.
+ * running_mean and running_var come as a pair: both NULL (training without a buffer update) or both set; one
+ * without the other is DS2_ERR_ARG.
+ * Limits (a launch's grid.y; beyond them DS2_ERR_ARG, nothing is launched): ds2_bn2d_stats C <= 65535;
+ * ds2_bn2d_apply_htanh B*C <= 65535 with layout_tbf=0, B <= 65535 with layout_tbf=1; ds2_bn2d_htanh_bwd B*C <= 65535.
  */
 size_t ds2_bn_ws_bytes(int C);
 /* conv flavour, x (B,C,inner) with inner = D*T */

@@ -395,15 +395,23 @@ def test_conv2_forward_families_agree(ops, monkeypatch, bsz, t1):
 
 
 # ------------------------------------------------------------------------------------------- BN
-@pytest.mark.parametrize('bsz,c,d,t', [(3, 32, 21, 57), (2, 32, 1, 3), (2, 32, 4, 8), (1, 32, 61, 131), (5, 32, 1, 2)])
-def test_bn2d_train_eval_and_backward(ops, bsz, c, d, t):
-    """(the planes of the 16-byte kernels start at every 4-byte offset: inner = d * t odd, < 4, a multiple of 4)"""
+@pytest.mark.parametrize('bsz,c,d,t,gb', [
+    pytest.param(3, 32, 21, 57, ((0.5, 1.5), (-1, 6)), id='3-32-21-57'),
+    pytest.param(2, 32, 1, 3, ((0.5, 1.5), (-1, 6)), id='2-32-1-3'),
+    pytest.param(2, 32, 4, 8, ((0.5, 1.5), (-1, 6)), id='2-32-4-8'),
+    pytest.param(1, 32, 61, 131, ((0.5, 1.5), (-1, 6)), id='1-32-61-131'),
+    pytest.param(5, 32, 1, 2, ((0.5, 1.5), (-1, 6)), id='5-32-1-2'),
+    pytest.param(3, 32, 21, 57, ((7, 9), (9, 11)), id='3-32-21-57-both-clamps')])
+def test_bn2d_train_eval_and_backward(ops, bsz, c, d, t, gb):
+    """(the planes of the 16-byte kernels start at every 4-byte offset: inner = d * t odd, < 4, a multiple of 4; with gamma in
+    [7, 9] and beta in [9, 11] a tenth of the elements sits on either side of Hardtanh(0, 20), with the other ranges none
+    reaches 20)"""
     rng = np.random.default_rng(20)
     x = torch.from_numpy((3 * rng.standard_normal((bsz, c, d, t)) + 5).astype(np.float32)).requires_grad_(True)
     bn = torch.nn.BatchNorm2d(c)
     with torch.no_grad():
-        bn.weight.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, c).astype(np.float32)))
-        bn.bias.copy_(torch.from_numpy(rng.uniform(-1, 6, c).astype(np.float32)))
+        bn.weight.copy_(torch.from_numpy(rng.uniform(*gb[0], c).astype(np.float32)))
+        bn.bias.copy_(torch.from_numpy(rng.uniform(*gb[1], c).astype(np.float32)))
     rm, rv = bn.running_mean.clone().to(DEV), bn.running_var.clone().to(DEV)
     y = F.hardtanh(bn(x), 0, 20)
     dy = torch.from_numpy(rng.standard_normal((bsz, c, d, t)).astype(np.float32))
