@@ -142,9 +142,15 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     were appended on the best hypothesis's surviving lineage (``BeamCTCDecoder`` reports the frame a prefix was first
     proposed, even by a proposal that was later pruned; the two agree unless a prefix of the best path left the beam and
     came back).  ``decode(probs, sizes)`` takes device tensors; ``last_scores`` / ``last_ctc_log_probs`` hold the fused
-    score (with the end-of-utterance LM terms) and the CTC log-probability of each best labelling."""
+    score (with the end-of-utterance LM terms) and the CTC log-probability of each best labelling.
 
-    def __init__(self, label_encoder, blank_index=0, beam_width=16, lm=None, alpha=0.0, beta=0.0, log_input=False):
+    ``booster``: a ``codes.bias.PhraseBooster`` made for the same alphabet and blank; the search then runs
+    ``ds2_ctc_beam_search_bias``, which adds ``weight * V(prefix)`` to the rank (include/ds2hip.h "phrase boosting"), and
+    ``last_bias_counts`` holds, per utterance, the labels of the returned labelling that the phrases cover.  Without one
+    nothing changes: the unbiased entry is called with the same arguments as ever."""
+
+    def __init__(self, label_encoder, blank_index=0, beam_width=16, lm=None, alpha=0.0, beta=0.0, log_input=False,
+                 booster=None):
         super().__init__(label_encoder, blank_index)
         if not 1 <= beam_width <= 128:
             raise ValueError('beam_width must be in 1..128 for the device search, got %d' % beam_width)
@@ -156,6 +162,22 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         self.space_id = classes.index(' ') if ' ' in classes else -1
         self.last_scores = None
         self.last_ctc_log_probs = None
+        self.booster, self.last_bias_counts = booster, None
+        if booster is not None:
+            have = [str(c) for c in booster.label_encoder.classes_.tolist()]
+            if have != classes or booster.blank_index != blank_index:
+                raise ValueError('the phrase booster was built for the alphabet %r with blank %d, the decoder has %r with '
+                                 'blank %d' % (have, booster.blank_index, classes, blank_index))
+
+    def _search(self, probs, sizes_d):
+        """The launch: the five device tensors of ``ops.ctc_beam_search`` and, with a booster, the bias counts (else None)."""
+        probs = probs.detach().contiguous().float()
+        if self.booster is None:
+            return ops.ctc_beam_search(probs, sizes_d, self.beam_width, self.blank_index, self.log_input, self.lm,
+                                       self.alpha, self.beta, self.space_id) + (None,)
+        trans, final = self.booster.tables(probs.device)
+        return ops.ctc_beam_search_bias(probs, sizes_d, self.beam_width, trans, final, self.booster.weight,
+                                        self.blank_index, self.log_input, self.lm, self.alpha, self.beta, self.space_id)
 
     def decode(self, probs, sizes=None):
         if not probs.is_cuda:
@@ -165,10 +187,10 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
             sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
         else:
             sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
-        labels, offs, lens, score, ctc = ops.ctc_beam_search(
-            probs.detach().contiguous().float(), sizes_d, self.beam_width, self.blank_index, self.log_input, self.lm,
-            self.alpha, self.beta, self.space_id)
+        labels, offs, lens, score, ctc, bias = self._search(probs, sizes_d)
         labels, offs, lens = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
+        if bias is not None:
+            self.last_bias_counts = bias.cpu().tolist()
         self.last_scores = score.cpu().tolist()
         self.last_ctc_log_probs = ctc.cpu().tolist()
         strings = [[self._to_string(labels[b, :lens[b]])] for b in range(bsz)]
@@ -178,7 +200,8 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     def decode_labels(self, probs, sizes=None):
         """``decode`` without the trip to the host: (labels (B,T) int32, lens (B,) int32) on the device, row b holding the
         label ids of ``decode``'s string b -- the layout ``ops.edit_stats`` scores.  Nothing waits on the stream, and
-        ``last_scores`` / ``last_ctc_log_probs`` are left as they were."""
+        ``last_scores`` / ``last_ctc_log_probs`` are left as they were; with a booster ``last_bias_counts`` is set to the
+        (B,) int32 DEVICE tensor of the counts."""
         if not probs.is_cuda:
             raise RuntimeError('DeviceBeamCTCDecoder.decode_labels runs on device tensors only')
         bsz, t, _ = probs.shape
@@ -186,7 +209,7 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
             sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
         else:
             sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
-        labels, _, lens, _, _ = ops.ctc_beam_search(
-            probs.detach().contiguous().float(), sizes_d, self.beam_width, self.blank_index, self.log_input, self.lm,
-            self.alpha, self.beta, self.space_id)
+        labels, _, lens, _, _, bias = self._search(probs, sizes_d)
+        if bias is not None:
+            self.last_bias_counts = bias
         return labels, lens

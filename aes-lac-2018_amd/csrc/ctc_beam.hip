@@ -1,6 +1,8 @@
 // Batched CTC prefix beam search on the device, with optional n-gram LM shallow fusion (ds2_ctc_beam_search_batch), and the
 // same search with the output rows decoupled from the utterances, each row with its own LM weights (ds2_ctc_beam_search_rows:
-// many (alpha, beta) pairs over one batch in one launch; DESIGN.md "LM weight tuning").
+// many (alpha, beta) pairs over one batch in one launch; DESIGN.md "LM weight tuning"), and the batch search with phrase
+// boosting (ds2_ctc_beam_search_bias: a context graph over the boosted phrases adds w * V(prefix) to a prefix's rank;
+// include/ds2hip.h and DESIGN.md "Phrase boosting").
 // Not in the reference (its test.py offers greedy / none); the host search ds2_ctc_beam_search (decode_host.hip) is the
 // no-LM yardstick and tests/beam_ref.py the pure-Python statement of the contract.  DESIGN.md "Device CTC beam search".
 //
@@ -138,6 +140,22 @@ __device__ double lm_delta(const LmArgs& lm, int c, int* ctx, int* n, uint64_t* 
     return lm.alpha * lp + lm.beta;
 }
 
+// phrase boosting: the context graph's tables (include/ds2hip.h "phrase boosting")
+struct BiasArgs {
+    const int32_t* trans;    // (states, A): next state | gain << 16; the blank column is never read
+    const int32_t* fin;      // (states): F(path(s)) - depth(s)
+    int states;
+    double weight;           // nats per matched label
+};
+
+// one step of the scan automaton: appending c in state *state; a next state outside [0, states) is taken as the root
+__device__ inline void bias_step(const BiasArgs& bias, int A, int c, int* state, int* count) {
+    const int32_t v = bias.trans[(size_t)*state * A + c];
+    const int next = v & 0xFFFF;
+    *state = next < bias.states ? next : 0;
+    *count += v >> 16;
+}
+
 struct BeamLds {
     double lp[MAX_A];
     double pb[MAX_W], pnb[MAX_W], tot[MAX_W], acc[MAX_W];   // acc = alpha * LM + beta * N so far
@@ -190,15 +208,19 @@ __device__ inline void stay_scores(const BeamLds& s, int i, int blank, double* n
 // ROWS = false: workgroup b decodes utterance b with the weights in lm_in (ds2_ctc_beam_search_batch).
 // ROWS = true: workgroup r decodes utterance utt[r] with alpha_r[r] / beta_r[r] into output row r and node array r
 // (ds2_ctc_beam_search_rows); everything after these first lines is the same code for both.
-template <bool ROWS>
+// BIAS = true (ds2_ctc_beam_search_bias): every beam entry also carries the context graph's (state, count) of its prefix,
+// both functions of the prefix alone, and w * (double)count joins its rank after log p + acc; at the end of the utterance
+// count + final[state] takes the place of count.  With BIAS = false none of this is compiled in.
+template <bool ROWS, bool BIAS>
 __global__ void __launch_bounds__(BEAM_THREADS)
 ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ sizes, int B, int T, int A, int blank, int W,
                 int log_input, LmArgs lm_in, const int32_t* __restrict__ utt, const float* __restrict__ alpha_r,
                 const float* __restrict__ beta_r, BeamNode* __restrict__ nodes_all, int32_t* __restrict__ out_labels,
                 int32_t* __restrict__ out_offsets, int32_t* __restrict__ out_len, float* __restrict__ out_score,
-                float* __restrict__ out_ctc) {
+                float* __restrict__ out_ctc, BiasArgs bias, int32_t* __restrict__ out_bias) {
     extern __shared__ __attribute__((aligned(16))) uint64_t keys[];   // W * A candidate keys
     __shared__ BeamLds s;
+    __shared__ int bstate[BIAS ? MAX_W : 1], bcount[BIAS ? MAX_W : 1];   // the context graph's state and V of each slot
     const int b = blockIdx.x, tid = threadIdx.x;      // b: the output row (and the node array); u: the utterance it decodes
     int u = b;
     LmArgs lm = lm_in;
@@ -241,6 +263,10 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
         s.node[0] = 0;
         s.wlen[0] = 0;
         s.nctx[0] = ctx_push(s.ctx[0], 0, ctx_cap, lm.bos);
+        if (BIAS) {
+            bstate[0] = 0;
+            bcount[0] = 0;
+        }
         nodes[0] = BeamNode{-1, -1, 0};
     }
     int nb = 1, node_count = 1;
@@ -279,7 +305,9 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
                 if (c == blank) {
                     double npb, npnb;
                     stay_scores(s, i, blank, &npb, &npnb);
-                    key = score_key(log_add(npb, npnb) + s.acc[i]);
+                    double v = log_add(npb, npnb) + s.acc[i];
+                    if (BIAS) v = v + bias.weight * (double)bcount[i];
+                    key = score_key(v);
                 } else if (s.lp[c] > NEG_INF) {
                     const double from = (c == s.last[i]) ? s.pb[i] : s.tot[i];
                     if (from > NEG_INF) {
@@ -292,7 +320,13 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
                             for (int q = 0; q < MAX_CTX; ++q) ctx[q] = s.ctx[i][q];
                             acc = acc + lm_delta(lm, c, ctx, &nctx, &wh, &wl);
                         }
-                        key = score_key(log_add(NEG_INF, from + s.lp[c]) + acc);
+                        double v = log_add(NEG_INF, from + s.lp[c]) + acc;
+                        if (BIAS) {
+                            int st = bstate[i], cnt = bcount[i];
+                            bias_step(bias, A, c, &st, &cnt);
+                            v = v + bias.weight * (double)cnt;
+                        }
+                        key = score_key(v);
                     }
                 }
             }
@@ -374,8 +408,13 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
         uint64_t r_hash = 0, r_phash = 0, r_whash = 0;
         int r_len = 0, r_last = 0, r_node = 0, r_wlen = 0, r_nctx = 0;
         int r_ctx[MAX_CTX];
+        int r_bstate = 0, r_bcount = 0;
         if (tid < keep) {
             const int k = s.sel[tid], i = k / A, c = k - i * A;
+            if (BIAS) {
+                r_bstate = bstate[i];
+                r_bcount = bcount[i];
+            }
             r_acc = s.acc[i];
             r_hash = s.hash[i];
             r_phash = s.phash[i];
@@ -394,6 +433,7 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
                 r_pb = NEG_INF;
                 r_pnb = log_add(NEG_INF, from + s.lp[c]);
                 if (lm.unit) r_acc = r_acc + lm_delta(lm, c, r_ctx, &r_nctx, &r_whash, &r_wlen);
+                if (BIAS) bias_step(bias, A, c, &r_bstate, &r_bcount);
                 r_phash = r_hash;
                 r_hash = ds2_hash_step(r_hash, c);
                 r_len += 1;
@@ -418,6 +458,10 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
             s.nctx[tid] = r_nctx;
 #pragma unroll
             for (int q = 0; q < MAX_CTX; ++q) s.ctx[tid][q] = r_ctx[q];
+            if (BIAS) {
+                bstate[tid] = r_bstate;
+                bcount[tid] = r_bcount;
+            }
         }
         nb = keep;
         node_count += new_nodes;
@@ -436,6 +480,10 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
             if (lm.unit == 2 && wl > 0) e = e + lm_delta(lm, lm.space, ctx, &nctx, &wh, &wl);
             int tok;
             e = e + lm.alpha * lm_log_prob(lm, ctx, nctx, lm.eos, &tok);
+        }
+        if (BIAS) {      // F = count + final[state]: what the prefix keeps once nothing can complete a pending phrase
+            bcount[tid] += bias.fin[bstate[tid]];
+            e = e + bias.weight * (double)bcount[tid];
         }
         s.pb[tid] = s.tot[tid] + e;     // reuse: end-adjusted score
     }
@@ -462,6 +510,7 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
         out_len[b] = len;
         out_score[b] = best >= 0 ? (float)best_v : (float)NEG_INF;
         out_ctc[b] = best >= 0 ? (float)s.tot[best] : (float)NEG_INF;
+        if (BIAS) out_bias[b] = best >= 0 ? bcount[best] : 0;
         s.need = len;
     }
     __syncthreads();
@@ -488,13 +537,14 @@ namespace {
         }                                                             \
     } while (0)
 
-// the checks and the launch both entries share; R workgroups, utt == nullptr for the batch entry (R == B)
+// the checks and the launch all entries share; R workgroups, utt == nullptr for the batch entry (R == B); bias != nullptr
+// for the phrase-boosting entry (its own arguments are checked there)
 int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B, int R, int T, int A, int blank,
                 int beam_width, int log_input, const void* ngram_table, int ngram_cap, const void* word_table, int word_cap,
                 int order, int unit, int bos_id, int eos_id, int unk_id, int space_id, float alpha, float beta,
                 float oov_logp, const int32_t* utt, const float* alpha_r, const float* beta_r, void* ws, size_t ws_bytes,
                 int32_t* out_labels, int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
-                void* stream) {
+                void* stream, const BiasArgs* bias = nullptr, int32_t* out_bias = nullptr) {
     if (beam_width < 1 || beam_width > MAX_W) {
         ds2_set_error("%s: beam_width %d is outside 1..%d", fn, beam_width, MAX_W);
         return DS2_ERR_ARG;
@@ -534,21 +584,27 @@ int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B,
     lm.beta = unit ? (double)beta : 0.0;
     lm.oov = (double)oov_logp;
     const size_t dyn = (size_t)beam_width * A * sizeof(uint64_t);
-    const void* kern = utt ? reinterpret_cast<const void*>(&ctc_beam_kernel<true>)
-                           : reinterpret_cast<const void*>(&ctc_beam_kernel<false>);
-    if (dyn + sizeof(BeamLds) > 64 * 1024 &&
+    const void* kern = bias  ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true>)
+                       : utt ? reinterpret_cast<const void*>(&ctc_beam_kernel<true, false>)
+                             : reinterpret_cast<const void*>(&ctc_beam_kernel<false, false>);
+    const size_t fixed = sizeof(BeamLds) + (bias ? 2 * MAX_W * sizeof(int) : 0);
+    if (dyn + fixed > 64 * 1024 &&
         hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
-        ds2_set_error("%s: %zu bytes of LDS are not available", fn, dyn + sizeof(BeamLds));
+        ds2_set_error("%s: %zu bytes of LDS are not available", fn, dyn + fixed);
         return DS2_ERR_LAUNCH;
     }
-    if (utt)
-        hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes, B, T,
-                           A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp);
+    if (bias)
+        hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
+                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias);
+    else if (utt)
+        hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
+                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr);
     else
-        hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes, B, T,
-                           A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp);
+        hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
+                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) {
         ds2_set_error("%s: launch failed: %s", fn, hipGetErrorString(e_));
@@ -590,4 +646,32 @@ extern "C" int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes
     return beam_launch("ds2_ctc_beam_search_rows", probs, sizes, B, R, T, A, blank, beam_width, log_input, ngram_table,
                        ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, 0.f, 0.f, oov_logp, utt,
                        alpha, beta, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream);
+}
+
+extern "C" int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                                        int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                                        const void* word_table, int word_cap, int order, int unit, int bos_id, int eos_id,
+                                        int unk_id, int space_id, float alpha, float beta, float oov_logp,
+                                        const int32_t* bias_trans, const int32_t* bias_final, int bias_states,
+                                        float bias_weight, void* ws, size_t ws_bytes, int32_t* out_labels,
+                                        int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
+                                        int32_t* out_bias, void* stream) {
+    const char* fn = "ds2_ctc_beam_search_bias";
+    if (bias_states < 1 || bias_states > DS2_BIAS_MAX_STATES) {
+        ds2_set_error("%s: %d context-graph states are outside 1..%d", fn, bias_states, DS2_BIAS_MAX_STATES);
+        return DS2_ERR_ARG;
+    }
+    if (!(bias_weight - bias_weight == 0.f)) {
+        ds2_set_error("%s: the weight %g is not finite", fn, (double)bias_weight);
+        return DS2_ERR_ARG;
+    }
+    if (!bias_trans || !bias_final || !out_bias) {
+        ds2_set_error("%s: bias_trans, bias_final and out_bias must not be NULL", fn);
+        return DS2_ERR_ARG;
+    }
+    BiasArgs bias{bias_trans, bias_final, bias_states, (double)bias_weight};
+    return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
+                       word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
+                       nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, &bias,
+                       out_bias);
 }

@@ -93,7 +93,9 @@ SIGNATURES = {
                                        _P, _Z, _P, _P, _P, _P, _P, _P]),
     'ds2_ctc_beam_search_rows': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F,
                                       _P, _Z, _P, _P, _P, _P, _P, _P]),
-    'ds2_edit_stats_ws_bytes': (_Z, [_I, _I, _I]),
+    'ds2_ctc_beam_search_bias': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F,
+                                      _P, _P, _I, _F, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
+    'ds2_edit_stats_ws_bytes':(_Z, [_I, _I, _I]),
     'ds2_edit_stats': (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _Z, _P, _P, _P]),
     'ds2_ctc_align_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_align': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
@@ -110,7 +112,8 @@ _lib = None
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3           # DS2_ERR_* of include/ds2hip.h
 ALIGN_BAND_MIN, ALIGN_BAND_MAX = 64, 8192                   # DS2_ALIGN_BAND_* of include/ds2hip.h (ds2_ctc_align_banded)
 KWS_MAX_LEN = 64                                            # DS2_KWS_MAX_LEN of include/ds2hip.h (ds2_ctc_keyword_search)
-EDIT_MAX_ITEMS = 2048                                       # DS2_EDIT_MAX_ITEMS of include/ds2hip.h (ds2_edit_stats)
+BIAS_MAX_LEN, BIAS_MAX_PHRASES, BIAS_MAX_STATES = 64, 1024, 32768   # DS2_BIAS_MAX_* of include/ds2hip.h (phrase boosting)
+EDIT_MAX_ITEMS = 2048                                      # DS2_EDIT_MAX_ITEMS of include/ds2hip.h (ds2_edit_stats)
 
 
 class Ds2Error(RuntimeError):

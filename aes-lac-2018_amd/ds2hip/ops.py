@@ -1098,6 +1098,41 @@ def ctc_beam_search_rows(probs, sizes, utt, alpha, beta, beam_width, blank=0, lo
     return labels, offsets, lens, score, ctc
 
 
+def ctc_beam_search_bias(probs, sizes, beam_width, bias_trans, bias_final, bias_weight, blank=0, log_input=False, lm=None,
+                         alpha=0.0, beta=0.0, space_id=-1):
+    """``ctc_beam_search`` with phrase boosting (``ds2_ctc_beam_search_bias``; include/ds2hip.h "phrase boosting"):
+    bias_trans (S,A) and bias_final (S,) int32 on the device are a context graph's tables (``codes.bias.ContextGraph``),
+    bias_weight the weight per matched label in nats.  Returns ``ctc_beam_search``'s five device tensors and bias (B,)
+    int32: the labels of each returned labelling that the boosted phrases cover.  Nothing waits on the stream."""
+    _require_device('ctc_beam_search_bias', torch.float32, probs=probs)
+    _require_device('ctc_beam_search_bias', torch.int32, sizes=sizes, bias_trans=bias_trans, bias_final=bias_final)
+    bsz, t, a = probs.shape
+    states = int(bias_final.numel())
+    if bias_trans.dim() != 2 or tuple(bias_trans.shape) != (states, a):
+        raise RuntimeError('ctc_beam_search_bias: bias_trans must be (states, A) = (%d, %d), got %s'
+                           % (states, a, tuple(bias_trans.shape)))
+    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
+    ws = _bytes_ws(ws_bytes, probs)
+    labels = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    offsets = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    lens = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
+    score = _empty((bsz,), probs)
+    ctc = _empty((bsz,), probs)
+    bias = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
+    if lm is None:
+        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
+    else:
+        tabs = lm.to(probs.device)
+        word = tabs.get('word')
+        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
+                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
+                   float(beta), float(lm.oov_logp))
+    lib.call('ds2_ctc_beam_search_bias', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
+             *lm_args, bias_trans, bias_final, states, float(bias_weight), ws, ws.numel() * ws.element_size(), labels,
+             offsets, lens, score, ctc, bias)
+    return labels, offsets, lens, score, ctc, bias
+
+
 EDIT_MAX_ITEMS = lib.EDIT_MAX_ITEMS     # DS2_EDIT_MAX_ITEMS of include/ds2hip.h: labels per side ds2_edit_stats takes
 EDIT_THREADS = 256                      # DS2_EDIT_THREADS: threads of its one workgroup per (row, level)
 EDIT_CHUNK = 8                          # DS2_EDIT_CHUNK: consecutive labels a thread owns in the item pass

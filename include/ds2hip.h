@@ -527,6 +527,49 @@ int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes, const int
                              size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
                              float* out_score, float* out_ctc_logp, void* stream);
 
+/* ds2_ctc_beam_search_bias: the batch search with phrase boosting (a context graph over a list of phrases).
+ * The rule ("phrase boosting"; a decision of this project).  Phrases are label sequences of 1..DS2_BIAS_MAX_LEN labels
+ * without the blank and without duplicates, at most DS2_BIAS_MAX_PHRASES of them; the trie of all their prefixes has at most
+ * DS2_BIAS_MAX_STATES nodes, root included.  For a label sequence y two integers are defined by a LEFTMOST-LONGEST,
+ * NON-OVERLAPPING scan.  Start with i = 0, m = 0 and repeat while i < len(y):
+ *   pending (V only)  if y[i:] is a node of the trie (a prefix of some phrase, complete or not), stop with
+ *                     V(y) = m + len(y) - i: a credit that is revocable;
+ *   otherwise         let l be the length of the longest phrase that is a prefix of y[i:]; if l > 0, m += l and i += l, else
+ *                     i += 1.
+ * If the loop ends without stopping, V(y) = m.  F(y) is the same scan without the pending rule: at every i it takes the
+ * longest complete phrase or steps by one, so F(y) is the number of labels of y covered by the chosen occurrences.
+ * The search ranks a prefix by  log(p_b + p_nb) + alpha * LM + beta * N + w * V(prefix);  at the end of the utterance w * F
+ * takes the place of w * V.  w = bias_weight, one float32 per matched label in nats, becomes a double once.  So a prefix
+ * earns credit label by label while it spells a phrase and loses the part that never became a complete phrase the moment
+ * it leaves the phrase: with NEW and NEW YORK boosted, NEW YOLK keeps 3, not 7.
+ * The scan is a deterministic automaton over the trie's nodes, since only the pending string can influence later
+ * decisions.  Nodes are numbered in BFS order, children in ascending label order, root = 0:
+ *   bias_trans (S, A) int32 on the device: entry [s][c] = next node (low 16 bits) | gain << 16 (high 16 bits, signed) with
+ *              gain = V(path(s) + c) - depth(s), in -63..+1.  The blank column is never read.
+ *   bias_final (S) int32: final[s] = F(path(s)) - depth(s) <= 0.
+ * Summing the gains along y gives V(y); adding final of the state reached gives F(y).  V and F stay integers in the
+ * kernel: every beam entry carries (state, count), both functions of the prefix alone (so merging stays sound), and the
+ * score term is w * (double)count, added after log p + acc, without fused multiply-adds: the bias never accumulates
+ * rounding.  At the end of the utterance w * (double)(count + final[state]) is added to the LM end terms.  The tie rules are
+ * those of ds2_ctc_beam_search_batch.
+ * S = bias_states, 1 <= S <= DS2_BIAS_MAX_STATES.  A next node outside [0, S) is taken as the root (checked on the device):
+ * a malformed table can give a wrong answer but never an out-of-range read.  out_bias (B) int32 = count + final[state] of
+ * the returned labelling (0 for the empty beam of an impossible input).  Every other argument and output is as for
+ * ds2_ctc_beam_search_batch, and so are its refusals; S out of range, a NULL table or out_bias, or a weight that is not
+ * finite are DS2_ERR_ARG with a message before any HIP call.  A root-only graph (S = 1, gains 0) or a weight of 0 gives the
+ * labels, offsets, lengths and scores of ds2_ctc_beam_search_batch.
+ * Added without a change of DS2_ABI_VERSION: one new symbol, no existing signature altered. */
+#define DS2_BIAS_MAX_LEN 64
+#define DS2_BIAS_MAX_PHRASES 1024
+#define DS2_BIAS_MAX_STATES 32768
+int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                             int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                             const void* word_table, int word_cap, int order, int unit, int bos_id, int eos_id,
+                             int unk_id, int space_id, float alpha, float beta, float oov_logp,
+                             const int32_t* bias_trans, const int32_t* bias_final, int bias_states, float bias_weight,
+                             void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
+                             float* out_score, float* out_ctc_logp, int32_t* out_bias, void* stream);
+
 /* ------------------------------------------------------------------ error counts from labels (csrc/edit_stats.hip)
  * Not in the reference (its test.py makes strings and calls python-Levenshtein per utterance).  Word and character error
  * counts of R hypothesis rows against their references in one launch, from label ids; no strings.

@@ -11,6 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
+from codes.bias import add_hotword_arguments, booster_from_arguments, check_hotword_arguments  # noqa: E402
 from codes.data import AudioDataLoader, AudioDataset  # noqa: E402
 from codes.decoder import BeamCTCDecoder, DeviceBeamCTCDecoder, GreedyDecoder  # noqa: E402
 from codes.transforms import BatchSpectrogram, waveform_scale  # noqa: E402
@@ -39,11 +40,13 @@ def main(argv=None):
     p.add_argument('--beam-device', action='store_true',
                    help='run --decoder beam as one batched device launch (implied by --lm-path); default: the host '
                         'search, one utterance at a time')
+    add_hotword_arguments(p)
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--output-path', default=None, type=str)
     args = p.parse_args(argv)
     if args.lm_path and args.decoder != 'beam':
         p.error('--lm-path needs --decoder beam: only the beam search can fuse a language model')
+    hotwords = check_hotword_arguments(p, args)
 
     ckpt = torch.load(args.model_path, map_location='cpu', weights_only=False)      # read once, for the check and the model
     ckpt_langs = checkpoint_langs(ckpt)
@@ -57,14 +60,15 @@ def main(argv=None):
     decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder),
                'beam': lambda: BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width),
                'none': lambda: None}[args.decoder]
-    if args.decoder == 'beam' and (args.lm_path or args.beam_device):
+    if args.decoder == 'beam' and (args.lm_path or args.beam_device or hotwords):
         def decoder():
             lm = None
             if args.lm_path:
                 from codes.lm import NGramLM
                 lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
+            booster = booster_from_arguments('test.py', args, target_t) if hotwords else None
             return DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                        beta=args.beta)
+                                        beta=args.beta, booster=booster)
     decoder = decoder()
     target_decoder = GreedyDecoder(target_t.label_encoder)
     dataset = AudioDataset(args.data_dir, args.manifest, transforms=val_t, target_transforms=target_t)

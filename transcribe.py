@@ -4,6 +4,7 @@
     python transcribe.py --model-path CKPT (--audio A.wav [B.wav ...] | --manifest M.csv [--data-dir DIR])
                          --output-path OUT.jsonl [--batch-size 32] [--decoder greedy|beam] [--beam-width W]
                          [--lm-path F --lm-unit U --alpha A --beta B] [--beam-device] [--resample]
+                         [--hotword PHRASE ...] [--hotwords FILE] [--hotword-weight W]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
 
@@ -17,7 +18,9 @@ centre of the model output step the decoder reports for it.  Model loading, ampl
 test.py's.  Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name (there is no resampling) -- unless
 ``--resample`` is given: a 16-bit PCM WAV of any supported rate and 1..8 channels is then uploaded as it is and converted to
 16 kHz mono on the device (``codes.transforms.Resample``, ``ds2_resample``) before it is segmented; the record gains
-``source_rate`` and ``source_channels``, and ``duration`` and all times refer to the 16 kHz samples."""
+``source_rate`` and ``source_channels``, and ``duration`` and all times refer to the 16 kHz samples.  ``--hotword`` /
+``--hotwords`` boost phrases in ``--decoder beam`` (``codes.bias.PhraseBooster``, the device search); the record gains
+``hotwords``, the phrases as normalised."""
 import argparse
 import json
 import os
@@ -31,6 +34,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
 from codes.align import ForcedAligner, group_words  # noqa: E402
+from codes.bias import add_hotword_arguments, booster_from_arguments, check_hotword_arguments  # noqa: E402
 
 SAMPLE_RATE = 16000
 
@@ -148,6 +152,7 @@ def main(argv=None):
     p.add_argument('--beta', default=1.0, type=float, help='bonus per LM token (default: 1.0; ignored without --lm-path)')
     p.add_argument('--beam-device', action='store_true',
                    help='run --decoder beam as one batched device launch (implied by --lm-path)')
+    add_hotword_arguments(p)
     p.add_argument('--max-segment', default=15.0, type=float, help='longest segment in seconds (default: 15)')
     p.add_argument('--min-speech', default=0.25, type=float, help='shorter speech is dropped, seconds (default: 0.25)')
     p.add_argument('--min-silence', default=0.3, type=float, help='shorter gaps are closed, seconds (default: 0.3)')
@@ -160,6 +165,7 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.lm_path and args.decoder != 'beam':
         p.error('--lm-path needs --decoder beam: only the beam search can fuse a language model')
+    hotwords = check_hotword_arguments(p, args)
     if args.batch_size < 1:
         p.error('--batch-size must be at least 1')
 
@@ -197,13 +203,14 @@ def main(argv=None):
     target_t = target_t[0]
     if args.decoder == 'greedy':
         decoder = GreedyDecoder(target_t.label_encoder)
-    elif args.lm_path or args.beam_device:
+    elif args.lm_path or args.beam_device or hotwords:
         lm = None
         if args.lm_path:
             from codes.lm import NGramLM
             lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
+        booster = booster_from_arguments('transcribe.py', args, target_t) if hotwords else None
         decoder = DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                       beta=args.beta)
+                                       beta=args.beta, booster=booster)
     else:
         decoder = BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
@@ -218,6 +225,8 @@ def main(argv=None):
                 raise SystemExit('transcribe.py: ' + str(e))
             rec = transcribe_samples(name, samples, model, frontend, decoder, segmenter, args.batch_size)
             rec.update(source)
+            if hotwords:
+                rec['hotwords'] = list(decoder.booster.keywords)
             n_seg += len(rec['segments'])
             out_f.write(json.dumps(rec) + '\n')
             out_f.flush()
