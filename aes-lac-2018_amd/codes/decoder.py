@@ -7,7 +7,8 @@ collapse (drop blank; drop a symbol equal to the previous FRAME's symbol) run on
 Edit distance replaces python-Levenshtein (absent here) with ``ds2_edit_distance`` (host C++ in libds2hip.so).
 ``BeamCTCDecoder`` (CTC prefix beam search, ``ds2_ctc_beam_search``) is an addition: the reference's ``test.py:21``
 offers greedy / none only.  ``DeviceBeamCTCDecoder`` runs the same search for a whole batch in one
-launch on the device (``ds2_ctc_beam_search_batch``), optionally fused with an n-gram LM (``codes.lm.NGramLM``).
+launch on the device (``ds2_ctc_beam_search_batch``), optionally fused with an n-gram LM (``codes.lm.NGramLM``); with
+``nbest=N`` it returns the N best entries of each final beam (``ds2_ctc_beam_search_nbest``).
 """
 import numpy as np
 import torch
@@ -23,6 +24,26 @@ def _levenshtein(a, b):
     ia = np.asarray([ids.setdefault(x, len(ids)) for x in a], dtype=np.int32)
     ib = np.asarray([ids.setdefault(x, len(ids)) for x in b], dtype=np.int32)
     return lib.host_call('ds2_edit_distance', ia, len(ia), ib, len(ib))
+
+
+def add_nbest_arguments(parser):
+    """The ``--nbest`` flag test.py and transcribe.py share."""
+    parser.add_argument('--nbest', default=None, type=int, metavar='N',
+                        help='alternatives per utterance from --decoder beam, best first, 1..--beam-width (runs the device '
+                             'search); default: 1')
+
+
+def check_nbest_arguments(parser, args):
+    """Refuse ``--nbest`` with any decoder that has no alternatives and outside 1..--beam-width; the N to use (1 if the
+    flag was not given: ``args.nbest`` stays None then)."""
+    if args.nbest is None:
+        return 1
+    if args.decoder != 'beam':
+        parser.error('--nbest needs --decoder beam: only the beam search has alternatives')
+    if not 1 <= args.nbest <= args.beam_width:
+        parser.error('--nbest %d is outside 1..--beam-width = 1..%d: the alternatives are entries of the final beam'
+                     % (args.nbest, args.beam_width))
+    return args.nbest
 
 
 class Decoder(object):
@@ -147,13 +168,30 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     ``booster``: a ``codes.bias.PhraseBooster`` made for the same alphabet and blank; the search then runs
     ``ds2_ctc_beam_search_bias``, which adds ``weight * V(prefix)`` to the rank (include/ds2hip.h "phrase boosting"), and
     ``last_bias_counts`` holds, per utterance, the labels of the returned labelling that the phrases cover.  Without one
-    nothing changes: the unbiased entry is called with the same arguments as ever."""
+    nothing changes: the unbiased entry is called with the same arguments as ever.
+
+    ``nbest`` (1..beam_width, default 1): with ``nbest > 1`` the search is ``ds2_ctc_beam_search_nbest`` and ``decode``
+    returns, per utterance, up to ``nbest`` alternatives, best first: the valid entries of the final beam ranked by the
+    fused score (include/ds2hip.h), so ``strings[b]`` and ``offsets[b]`` have ``max(1, count[b])`` entries and entry 0 is
+    what ``nbest == 1`` returns (an impossible input keeps its one empty string).  ``last_scores``,
+    ``last_ctc_log_probs`` and ``last_bias_counts`` stay the per-utterance values of entry 0; ``last_nbest_scores[b]``,
+    ``last_nbest_ctc_log_probs[b]``, ``last_nbest_bias_counts[b]`` (with a booster) and ``last_nbest_posteriors[b]`` are
+    lists as long as ``strings[b]``.  The posterior of alternative n is ``exp(s_n - logsumexp(s_0 .. s_{count-1}))`` over
+    the returned float32 fused scores, in float64 (``nbest_posteriors``): a weight AMONG THE RETURNED ALTERNATIVES UNDER
+    THE FUSED SCORE, not a calibrated probability -- the score holds alpha, beta and the boost, the list ends at
+    ``nbest``, and nobody has measured its calibration on a trained model.  With ``nbest == 1`` nothing changes: the
+    1-best entries are called with the arguments they get today and the ``last_nbest_*`` fields stay None."""
 
     def __init__(self, label_encoder, blank_index=0, beam_width=16, lm=None, alpha=0.0, beta=0.0, log_input=False,
-                 booster=None):
+                 booster=None, nbest=1):
         super().__init__(label_encoder, blank_index)
         if not 1 <= beam_width <= 128:
             raise ValueError('beam_width must be in 1..128 for the device search, got %d' % beam_width)
+        if not 1 <= nbest <= beam_width:
+            raise ValueError('nbest must be in 1..beam_width = 1..%d, got %d' % (beam_width, nbest))
+        self.nbest = int(nbest)
+        self.last_nbest_scores = self.last_nbest_ctc_log_probs = None
+        self.last_nbest_bias_counts = self.last_nbest_posteriors = None
         self.beam_width, self.log_input = int(beam_width), bool(log_input)
         self.lm, self.alpha, self.beta = lm, float(alpha), float(beta)
         classes = [str(c) for c in self.label_encoder.classes_.tolist()]
@@ -179,6 +217,48 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         return ops.ctc_beam_search_bias(probs, sizes_d, self.beam_width, trans, final, self.booster.weight,
                                         self.blank_index, self.log_input, self.lm, self.alpha, self.beta, self.space_id)
 
+    def _search_nbest(self, probs, sizes_d):
+        """The N-best launch: the seven device tensors of ``ops.ctc_beam_search_nbest``."""
+        probs = probs.detach().contiguous().float()
+        trans, final, weight = None, None, 0.0
+        if self.booster is not None:
+            trans, final = self.booster.tables(probs.device)
+            weight = self.booster.weight
+        return ops.ctc_beam_search_nbest(probs, sizes_d, self.beam_width, self.nbest, self.blank_index, self.log_input,
+                                         self.lm, self.alpha, self.beta, self.space_id, trans, final, weight)
+
+    @staticmethod
+    def nbest_posteriors(scores):
+        """``exp(s_n - logsumexp(s))`` in float64 from the returned float32 fused scores; ``[0.0]`` for no alternatives.
+        A weight among these alternatives under the fused score, not a calibrated probability."""
+        s = np.asarray(scores, dtype=np.float32).astype(np.float64)
+        if s.size == 0:
+            return [0.0]
+        m = s.max()
+        if not np.isfinite(m):                                 # every score beyond float32: the formula has no value
+            return [1.0 / s.size] * s.size
+        e = np.exp(s - m)                                      # the same number with the maximum taken out first
+        return (e / e.sum()).tolist()
+
+    def _decode_nbest(self, probs, sizes_d):
+        bsz = probs.shape[0]
+        labels, offs, lens, score, ctc, bias, count = self._search_nbest(probs, sizes_d)
+        labels, offs, lens, count = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy(), count.cpu().numpy()
+        score, ctc = score.cpu().numpy(), ctc.cpu().numpy()
+        keep = [max(1, int(c)) for c in count]
+        self.last_scores = score[:, 0].tolist()
+        self.last_ctc_log_probs = ctc[:, 0].tolist()
+        self.last_nbest_scores = [score[b, :keep[b]].tolist() for b in range(bsz)]
+        self.last_nbest_ctc_log_probs = [ctc[b, :keep[b]].tolist() for b in range(bsz)]
+        self.last_nbest_posteriors = [self.nbest_posteriors(score[b, :int(count[b])]) for b in range(bsz)]
+        if bias is not None:
+            bias = bias.cpu().numpy()
+            self.last_bias_counts = bias[:, 0].tolist()
+            self.last_nbest_bias_counts = [bias[b, :keep[b]].tolist() for b in range(bsz)]
+        strings = [[self._to_string(labels[b, n, :lens[b, n]]) for n in range(keep[b])] for b in range(bsz)]
+        offsets = [[torch.IntTensor(offs[b, n, :lens[b, n]].copy()) for n in range(keep[b])] for b in range(bsz)]
+        return strings, offsets
+
     def decode(self, probs, sizes=None):
         if not probs.is_cuda:
             raise RuntimeError('DeviceBeamCTCDecoder.decode runs on device tensors only')
@@ -187,6 +267,8 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
             sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
         else:
             sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+        if self.nbest > 1:
+            return self._decode_nbest(probs, sizes_d)
         labels, offs, lens, score, ctc, bias = self._search(probs, sizes_d)
         labels, offs, lens = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
         if bias is not None:
@@ -213,3 +295,18 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         if bias is not None:
             self.last_bias_counts = bias
         return labels, lens
+
+    def decode_labels_nbest(self, probs, sizes=None):
+        """The alternatives without the trip to the host: (labels (B,N,T) int32, lens (B,N) int32, count (B,) int32) on
+        the device, N = ``nbest``, rows [0, count[b]) of utterance b best first and the rest empty.  Viewed as (B*N, T) and
+        (B*N,) that is the layout ``ops.edit_stats`` scores with ``ref_index = arange(B*N) // N``.  Nothing waits on the
+        stream and no ``last_*`` field is touched."""
+        if not probs.is_cuda:
+            raise RuntimeError('DeviceBeamCTCDecoder.decode_labels_nbest runs on device tensors only')
+        bsz, t, _ = probs.shape
+        if sizes is None:
+            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
+        else:
+            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+        labels, _, lens, _, _, _, count = self._search_nbest(probs, sizes_d)
+        return labels, lens, count

@@ -2,7 +2,8 @@
 // same search with the output rows decoupled from the utterances, each row with its own LM weights (ds2_ctc_beam_search_rows:
 // many (alpha, beta) pairs over one batch in one launch; DESIGN.md "LM weight tuning"), and the batch search with phrase
 // boosting (ds2_ctc_beam_search_bias: a context graph over the boosted phrases adds w * V(prefix) to a prefix's rank;
-// include/ds2hip.h and DESIGN.md "Phrase boosting").
+// include/ds2hip.h and DESIGN.md "Phrase boosting"), and the batch search, boosted or not, that returns the N best entries
+// of the final beam instead of one (ds2_ctc_beam_search_nbest; include/ds2hip.h and DESIGN.md "N-best lists").
 // Not in the reference (its test.py offers greedy / none); the host search ds2_ctc_beam_search (decode_host.hip) is the
 // no-LM yardstick and tests/beam_ref.py the pure-Python statement of the contract.  DESIGN.md "Device CTC beam search".
 //
@@ -205,19 +206,85 @@ __device__ inline void stay_scores(const BeamLds& s, int i, int blank, double* n
     *npnb = q;
 }
 
+// The end of ds2_ctc_beam_search_nbest, called by all 256 threads after the last frame with s.pb[i] = the end-adjusted score
+// of slot i < nb (and bcount[i] = count + final[state] where bcount is given).  A function of its own, not inlined, so
+// that the frame loop of the NBEST instantiations is compiled as that of the 1-best ones.
+// Ranking by counting: thread i < nb compares its score with all others in LDS; s.sel (free after the last frame) maps
+// rank -> slot, -1 where fewer than nbest entries are valid.  The valid entries' ranks are 0 .. valid-1, each once, so rows
+// [0, count) have a slot and the rest have none.
+__device__ __noinline__ void nbest_end(BeamLds& s, const int* bcount, int nb, int nbest, int b, int T, const BeamNode* nodes,
+                                       int32_t* out_labels, int32_t* out_offsets, int32_t* out_len, float* out_score,
+                                       float* out_ctc, int32_t* out_bias, int32_t* out_count) {
+    const int tid = threadIdx.x;
+    if (tid < nbest) s.sel[tid] = -1;
+    __syncthreads();
+    int rank = -1;
+    if (tid < nb) {
+        const double v = s.pb[tid];
+        if (v > NEG_INF) {          // what the single pick can choose; false for a NaN
+            rank = 0;
+            for (int j = 0; j < nb; ++j) {
+                const double o = s.pb[j];
+                rank += (o > v) || (o == v && j < tid);
+            }
+            if (rank < nbest) s.sel[rank] = tid;
+        }
+    }
+    __syncthreads();
+    if (tid < nbest) {
+        const size_t row = (size_t)b * nbest + tid;
+        const int slot = s.sel[tid];
+        if (slot < 0) {
+            out_len[row] = 0;
+            out_score[row] = (float)NEG_INF;
+            out_ctc[row] = (float)NEG_INF;
+            if (bcount) out_bias[row] = 0;
+        }
+        if (slot >= 0 ? (tid + 1 == nbest || s.sel[tid + 1] < 0) : tid == 0) out_count[b] = slot >= 0 ? tid + 1 : 0;
+    }
+    if (rank >= 0 && rank < nbest) {      // up to 128 chains at once (two waves), each followed by the thread that owns the slot
+        const size_t row = (size_t)b * nbest + rank;
+        const int len = s.len[tid];
+        int nd = s.node[tid];
+        for (int q = len - 1; q >= 0; --q) {
+            const BeamNode e = nodes[nd];
+            out_labels[row * T + q] = e.sym;
+            out_offsets[row * T + q] = e.frame;
+            nd = e.parent;
+        }
+        out_len[row] = len;
+        out_score[row] = (float)s.pb[tid];
+        out_ctc[row] = (float)s.tot[tid];
+        if (bcount) out_bias[row] = bcount[tid];
+    }
+    for (int r = 0; r < nbest; ++r) {     // zeros past every row's length, by the whole workgroup
+        const size_t row = (size_t)b * nbest + r;
+        const int slot = s.sel[r];
+        for (int q = (slot >= 0 ? s.len[slot] : 0) + tid; q < T; q += BEAM_THREADS) {
+            out_labels[row * T + q] = 0;
+            out_offsets[row * T + q] = 0;
+        }
+    }
+}
+
 // ROWS = false: workgroup b decodes utterance b with the weights in lm_in (ds2_ctc_beam_search_batch).
 // ROWS = true: workgroup r decodes utterance utt[r] with alpha_r[r] / beta_r[r] into output row r and node array r
 // (ds2_ctc_beam_search_rows); everything after these first lines is the same code for both.
 // BIAS = true (ds2_ctc_beam_search_bias): every beam entry also carries the context graph's (state, count) of its prefix,
 // both functions of the prefix alone, and w * (double)count joins its rank after log p + acc; at the end of the utterance
 // count + final[state] takes the place of count.  With BIAS = false none of this is compiled in.
-template <bool ROWS, bool BIAS>
+// NBEST = true (ds2_ctc_beam_search_nbest): the same frames; after the last one the valid entries of the final beam are
+// ranked by counting (higher end-adjusted score first, an exact tie to the lower slot) and the entry of rank n < nbest
+// follows its own node chain back into output row b * nbest + n.  With NBEST = false nbest and out_count are not read and
+// the end is the single pick below.
+template <bool ROWS, bool BIAS, bool NBEST = false>
 __global__ void __launch_bounds__(BEAM_THREADS)
 ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ sizes, int B, int T, int A, int blank, int W,
                 int log_input, LmArgs lm_in, const int32_t* __restrict__ utt, const float* __restrict__ alpha_r,
                 const float* __restrict__ beta_r, BeamNode* __restrict__ nodes_all, int32_t* __restrict__ out_labels,
                 int32_t* __restrict__ out_offsets, int32_t* __restrict__ out_len, float* __restrict__ out_score,
-                float* __restrict__ out_ctc, BiasArgs bias, int32_t* __restrict__ out_bias) {
+                float* __restrict__ out_ctc, BiasArgs bias, int32_t* __restrict__ out_bias, int nbest,
+                int32_t* __restrict__ out_count) {
     extern __shared__ __attribute__((aligned(16))) uint64_t keys[];   // W * A candidate keys
     __shared__ BeamLds s;
     __shared__ int bstate[BIAS ? MAX_W : 1], bcount[BIAS ? MAX_W : 1];   // the context graph's state and V of each slot
@@ -488,6 +555,11 @@ ctc_beam_kernel(const float* __restrict__ probs, const int32_t* __restrict__ siz
         s.pb[tid] = s.tot[tid] + e;     // reuse: end-adjusted score
     }
     __syncthreads();
+    if (NBEST) {
+        nbest_end(s, BIAS ? bcount : nullptr, nb, nbest, b, T, nodes, out_labels, out_offsets, out_len, out_score, out_ctc,
+                  out_bias, out_count);
+        return;
+    }
     if (tid == 0) {
         int best = -1;
         double best_v = NEG_INF;
@@ -538,13 +610,15 @@ namespace {
     } while (0)
 
 // the checks and the launch all entries share; R workgroups, utt == nullptr for the batch entry (R == B); bias != nullptr
-// for the phrase-boosting entry (its own arguments are checked there)
+// for the phrase-boosting entry (its own arguments are checked there); nbest > 0 for the N-best entry (batch form only,
+// boosted or not: its outputs have nbest rows per utterance)
 int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B, int R, int T, int A, int blank,
                 int beam_width, int log_input, const void* ngram_table, int ngram_cap, const void* word_table, int word_cap,
                 int order, int unit, int bos_id, int eos_id, int unk_id, int space_id, float alpha, float beta,
                 float oov_logp, const int32_t* utt, const float* alpha_r, const float* beta_r, void* ws, size_t ws_bytes,
                 int32_t* out_labels, int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
-                void* stream, const BiasArgs* bias = nullptr, int32_t* out_bias = nullptr) {
+                void* stream, const BiasArgs* bias = nullptr, int32_t* out_bias = nullptr, int nbest = 0,
+                int32_t* out_count = nullptr) {
     if (beam_width < 1 || beam_width > MAX_W) {
         ds2_set_error("%s: beam_width %d is outside 1..%d", fn, beam_width, MAX_W);
         return DS2_ERR_ARG;
@@ -584,7 +658,9 @@ int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B,
     lm.beta = unit ? (double)beta : 0.0;
     lm.oov = (double)oov_logp;
     const size_t dyn = (size_t)beam_width * A * sizeof(uint64_t);
-    const void* kern = bias  ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true>)
+    const void* kern = nbest ? (bias ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true, true>)
+                                     : reinterpret_cast<const void*>(&ctc_beam_kernel<false, false, true>))
+                       : bias  ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true>)
                        : utt ? reinterpret_cast<const void*>(&ctc_beam_kernel<true, false>)
                              : reinterpret_cast<const void*>(&ctc_beam_kernel<false, false>);
     const size_t fixed = sizeof(BeamLds) + (bias ? 2 * MAX_W * sizeof(int) : 0);
@@ -593,18 +669,26 @@ int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B,
         ds2_set_error("%s: %zu bytes of LDS are not available", fn, dyn + fixed);
         return DS2_ERR_LAUNCH;
     }
-    if (bias)
+    if (nbest && bias)
+        hipLaunchKernelGGL((ctc_beam_kernel<false, true, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs,
+                           sizes, B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias, nbest, out_count);
+    else if (nbest)
+        hipLaunchKernelGGL((ctc_beam_kernel<false, false, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs,
+                           sizes, B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
+                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, nbest, out_count);
+    else if (bias)
         hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
                            B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias);
+                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias, 0, nullptr);
     else if (utt)
         hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
                            B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr);
+                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, 0, nullptr);
     else
         hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
                            B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr);
+                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, 0, nullptr);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) {
         ds2_set_error("%s: launch failed: %s", fn, hipGetErrorString(e_));
@@ -674,4 +758,45 @@ extern "C" int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes
                        word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
                        nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, &bias,
                        out_bias);
+}
+
+extern "C" int ds2_ctc_beam_search_nbest(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                                         int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                                         const void* word_table, int word_cap, int order, int unit, int bos_id, int eos_id,
+                                         int unk_id, int space_id, float alpha, float beta, float oov_logp,
+                                         const int32_t* bias_trans, const int32_t* bias_final, int bias_states,
+                                         float bias_weight, int nbest, void* ws, size_t ws_bytes, int32_t* out_labels,
+                                         int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
+                                         int32_t* out_bias, int32_t* out_count, void* stream) {
+    const char* fn = "ds2_ctc_beam_search_nbest";
+    if (nbest < 1 || nbest > beam_width) {
+        ds2_set_error("%s: nbest %d is outside 1..beam_width = %d", fn, nbest, beam_width);
+        return DS2_ERR_ARG;
+    }
+    if (!out_count) {
+        ds2_set_error("%s: out_count must not be NULL", fn);
+        return DS2_ERR_ARG;
+    }
+    if (!bias_trans)      // no boosting: the other bias arguments and out_bias are ignored
+        return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
+                           word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
+                           nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, nullptr,
+                           nullptr, nbest, out_count);
+    if (bias_states < 1 || bias_states > DS2_BIAS_MAX_STATES) {
+        ds2_set_error("%s: %d context-graph states are outside 1..%d", fn, bias_states, DS2_BIAS_MAX_STATES);
+        return DS2_ERR_ARG;
+    }
+    if (!(bias_weight - bias_weight == 0.f)) {
+        ds2_set_error("%s: the weight %g is not finite", fn, (double)bias_weight);
+        return DS2_ERR_ARG;
+    }
+    if (!bias_final || !out_bias) {
+        ds2_set_error("%s: with bias_trans, bias_final and out_bias must not be NULL", fn);
+        return DS2_ERR_ARG;
+    }
+    BiasArgs bias{bias_trans, bias_final, bias_states, (double)bias_weight};
+    return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
+                       word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
+                       nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, &bias,
+                       out_bias, nbest, out_count);
 }

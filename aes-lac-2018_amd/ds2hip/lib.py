@@ -95,6 +95,8 @@ SIGNATURES = {
                                       _P, _Z, _P, _P, _P, _P, _P, _P]),
     'ds2_ctc_beam_search_bias': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F,
                                       _P, _P, _I, _F, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
+    'ds2_ctc_beam_search_nbest': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F,
+                                       _P, _P, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
     'ds2_edit_stats_ws_bytes':(_Z, [_I, _I, _I]),
     'ds2_edit_stats': (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _Z, _P, _P, _P]),
     'ds2_ctc_align_ws_bytes': (_Z, [_I, _I, _I]),

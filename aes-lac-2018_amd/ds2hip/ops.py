@@ -1133,6 +1133,52 @@ def ctc_beam_search_bias(probs, sizes, beam_width, bias_trans, bias_final, bias_
     return labels, offsets, lens, score, ctc, bias
 
 
+def ctc_beam_search_nbest(probs, sizes, beam_width, nbest, blank=0, log_input=False, lm=None, alpha=0.0, beta=0.0,
+                          space_id=-1, bias_trans=None, bias_final=None, bias_weight=0.0):
+    """``ctc_beam_search`` -- with ``bias_trans`` / ``bias_final`` / ``bias_weight``, ``ctc_beam_search_bias`` -- returning
+    the ``nbest`` best entries of each utterance's final beam (``ds2_ctc_beam_search_nbest``; include/ds2hip.h has the
+    ranking).  1 <= nbest <= beam_width.  Returns the device tensors labels (B,N,T), offsets (B,N,T), lens (B,N) int32,
+    score, ctc_logp (B,N) fp32, bias (B,N) int32 (None without a graph) and count (B,) int32: rows [0, count[b]) of
+    utterance b are its alternatives, best first, row 0 bit-identical to the 1-best search; the rows past the count are
+    empty at -inf.  Nothing waits on the stream."""
+    _require_device('ctc_beam_search_nbest', torch.float32, probs=probs)
+    _require_device('ctc_beam_search_nbest', torch.int32, sizes=sizes)
+    bsz, t, a = probs.shape
+    n = int(nbest)
+    if not 1 <= n <= int(beam_width):
+        raise ValueError('ctc_beam_search_nbest: nbest %d is outside 1..beam_width = %d' % (n, int(beam_width)))
+    bias, bias_args = None, (None, None, 0, 0.0)
+    if bias_trans is not None:
+        if bias_final is None:
+            raise RuntimeError('ctc_beam_search_nbest: bias_trans needs bias_final')
+        _require_device('ctc_beam_search_nbest', torch.int32, bias_trans=bias_trans, bias_final=bias_final)
+        states = int(bias_final.numel())
+        if bias_trans.dim() != 2 or tuple(bias_trans.shape) != (states, a):
+            raise RuntimeError('ctc_beam_search_nbest: bias_trans must be (states, A) = (%d, %d), got %s'
+                               % (states, a, tuple(bias_trans.shape)))
+        bias = torch.empty((bsz, n), dtype=torch.int32, device=probs.device)
+        bias_args = (bias_trans, bias_final, states, float(bias_weight))
+    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
+    ws = _bytes_ws(ws_bytes, probs)
+    labels = torch.empty((bsz, n, t), dtype=torch.int32, device=probs.device)
+    offsets = torch.empty((bsz, n, t), dtype=torch.int32, device=probs.device)
+    lens = torch.empty((bsz, n), dtype=torch.int32, device=probs.device)
+    score = _empty((bsz, n), probs)
+    ctc = _empty((bsz, n), probs)
+    count = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
+    if lm is None:
+        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
+    else:
+        tabs = lm.to(probs.device)
+        word = tabs.get('word')
+        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
+                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
+                   float(beta), float(lm.oov_logp))
+    lib.call('ds2_ctc_beam_search_nbest', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
+             *lm_args, *bias_args, n, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc, bias, count)
+    return labels, offsets, lens, score, ctc, bias, count
+
+
 EDIT_MAX_ITEMS = lib.EDIT_MAX_ITEMS     # DS2_EDIT_MAX_ITEMS of include/ds2hip.h: labels per side ds2_edit_stats takes
 EDIT_THREADS = 256                      # DS2_EDIT_THREADS: threads of its one workgroup per (row, level)
 EDIT_CHUNK = 8                          # DS2_EDIT_CHUNK: consecutive labels a thread owns in the item pass

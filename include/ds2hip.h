@@ -570,6 +570,42 @@ int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes, int B, in
                              void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets, int32_t* out_len,
                              float* out_score, float* out_ctc_logp, int32_t* out_bias, void* stream);
 
+/* ds2_ctc_beam_search_nbest: the batch search that returns the N best entries of its final beam, not one.
+ * Same search.  Frame by frame this is the search of ds2_ctc_beam_search_batch and, with a non-NULL bias_trans, that of
+ * ds2_ctc_beam_search_bias: the beam, the merging, the LM and bias terms, the fp64 scores and the tie rules at the cut are
+ * theirs.  Only the end differs.
+ * Valid entries.  After the last frame slot i of the final beam has its end-adjusted score v_i = log(p_b + p_nb) + the LM
+ * terms with the end-of-utterance ones + w * F, the number the 1-best entries pick by.  Slot i is VALID if v_i > -1e300, the
+ * condition under which that pick can choose it; a NaN is not valid.
+ * Ranking.  rank_i = #{valid j : v_j > v_i} + #{valid j < i : v_j == v_i}: a higher score comes first, an exact tie goes to
+ * the lower slot.  out_count[b] = min(nbest, number of valid slots).
+ * Rows.  Outputs have nbest rows per utterance: out_labels / out_offsets (B,N,T) int32, out_len (B,N) int32, out_score /
+ * out_ctc_logp (B,N) float32, out_bias (B,N) int32, out_count (B) int32.  Row n < out_count[b] holds the slot of rank n: its
+ * labels, the frame each label was appended at on ITS OWN surviving lineage, its length, (float)v, (float)log(p_b + p_nb)
+ * and, with boosting, count + final[state].  Row 0 is bit for bit what the 1-best entry (_batch, or _bias with a graph)
+ * writes for that utterance.  Rows n >= out_count[b] have length 0, score and ctc_logp -inf (as the 1-best entries write for
+ * an impossible input) and bias 0.  Every row is zero past its length in out_labels and out_offsets.  The rows of one
+ * utterance are distinct labellings, since the final beam holds each prefix once (up to the 64-bit hash collision that the
+ * merge of csrc/ctc_beam.hip admits).
+ * Limits.  1 <= nbest <= beam_width; ws >= ds2_ctc_beam_ws_bytes(B, T, beam_width): the workspace is that of the 1-best
+ * entries, whose node arrays already hold every lineage.
+ * Refusals, DS2_ERR_ARG with a message before any HIP call: nbest out of range (the message names nbest and beam_width); a
+ * NULL output or a NULL out_count; with a non-NULL bias_trans what ds2_ctc_beam_search_bias refuses (states out of range, a
+ * NULL bias_final or out_bias, a weight that is not finite); and everything the batch entry refuses, under this function's
+ * name.  With bias_trans == NULL there is no boosting: bias_final, bias_states, bias_weight and out_bias are ignored and
+ * out_bias is not written.  B = 0 is DS2_OK.
+ * Determinism.  Results are bit-identical from run to run and do not depend on the other utterances, on the workspace's
+ * contents or on what the outputs held; nothing outside the stated output extents is written.
+ * Added without a change of DS2_ABI_VERSION: one new symbol, no existing signature altered. */
+int ds2_ctc_beam_search_nbest(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
+                              int beam_width, int log_input, const void* ngram_table, int ngram_cap,
+                              const void* word_table, int word_cap, int order, int unit, int bos_id, int eos_id,
+                              int unk_id, int space_id, float alpha, float beta, float oov_logp,
+                              const int32_t* bias_trans, const int32_t* bias_final, int bias_states, float bias_weight,
+                              int nbest, void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets,
+                              int32_t* out_len, float* out_score, float* out_ctc_logp, int32_t* out_bias,
+                              int32_t* out_count, void* stream);
+
 /* ------------------------------------------------------------------ error counts from labels (csrc/edit_stats.hip)
  * Not in the reference (its test.py makes strings and calls python-Levenshtein per utterance).  Word and character error
  * counts of R hypothesis rows against their references in one launch, from label ids; no strings.

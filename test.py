@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Evaluation CLI with the reference's flags (reference ``test.py:12-26``): greedy-decode a manifest with a trained
-checkpoint and report corpus-level WER / CER (``test.py:81-104``: total edits / total reference words, chars)."""
+checkpoint and report corpus-level WER / CER (``test.py:81-104``: total edits / total reference words, chars).
+Additions: ``--decoder beam`` with ``--lm-path``, ``--hotword`` and ``--nbest N`` (the device search; with ``--nbest`` an
+``Oracle Summary`` line follows the ``Test Summary``: the best of each utterance's N alternatives, WER and CER
+independently; ``--nbest-path`` writes the alternatives as JSON lines)."""
 import argparse
+import json
 import os
 import sys
 
@@ -13,7 +17,8 @@ sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
 from codes.bias import add_hotword_arguments, booster_from_arguments, check_hotword_arguments  # noqa: E402
 from codes.data import AudioDataLoader, AudioDataset  # noqa: E402
-from codes.decoder import BeamCTCDecoder, DeviceBeamCTCDecoder, GreedyDecoder  # noqa: E402
+from codes.decoder import (BeamCTCDecoder, DeviceBeamCTCDecoder, GreedyDecoder, add_nbest_arguments,  # noqa: E402
+                           check_nbest_arguments)
 from codes.transforms import BatchSpectrogram, waveform_scale  # noqa: E402
 from codes.utils.model_utils import checkpoint_langs, load_model  # noqa: E402
 
@@ -41,12 +46,19 @@ def main(argv=None):
                    help='run --decoder beam as one batched device launch (implied by --lm-path); default: the host '
                         'search, one utterance at a time')
     add_hotword_arguments(p)
+    add_nbest_arguments(p)
+    p.add_argument('--nbest-path', default=None, type=str, metavar='FILE',
+                   help='with --decoder beam: write one JSON line per utterance, {"reference", "alternatives": [{"text", '
+                        '"score", "ctc_logp", "posterior"}]}, for an external rescorer (runs the device search)')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--output-path', default=None, type=str)
     args = p.parse_args(argv)
     if args.lm_path and args.decoder != 'beam':
         p.error('--lm-path needs --decoder beam: only the beam search can fuse a language model')
     hotwords = check_hotword_arguments(p, args)
+    nbest = check_nbest_arguments(p, args)
+    if args.nbest_path and args.decoder != 'beam':
+        p.error('--nbest-path needs --decoder beam: only the beam search has alternatives')
 
     ckpt = torch.load(args.model_path, map_location='cpu', weights_only=False)      # read once, for the check and the model
     ckpt_langs = checkpoint_langs(ckpt)
@@ -60,7 +72,8 @@ def main(argv=None):
     decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder),
                'beam': lambda: BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width),
                'none': lambda: None}[args.decoder]
-    if args.decoder == 'beam' and (args.lm_path or args.beam_device or hotwords):
+    want_nbest = args.nbest is not None or bool(args.nbest_path)       # either flag runs the device search
+    if args.decoder == 'beam' and (args.lm_path or args.beam_device or hotwords or want_nbest):
         def decoder():
             lm = None
             if args.lm_path:
@@ -68,7 +81,7 @@ def main(argv=None):
                 lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
             booster = booster_from_arguments('test.py', args, target_t) if hotwords else None
             return DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                        beta=args.beta, booster=booster)
+                                        beta=args.beta, booster=booster, nbest=nbest)
     decoder = decoder()
     target_decoder = GreedyDecoder(target_t.label_encoder)
     dataset = AudioDataset(args.data_dir, args.manifest, transforms=val_t, target_transforms=target_t)
@@ -76,6 +89,8 @@ def main(argv=None):
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
 
     total_cer = total_wer = num_tokens = num_chars = 0
+    oracle_wer = oracle_cer = 0                     # --nbest: the best alternative per utterance, WER and CER independently
+    nbest_lines = []
     output_data = []
     for wavs, targets, _, target_sizes in loader:
         inputs, input_percentages = frontend(wavs)
@@ -95,6 +110,18 @@ def main(argv=None):
             total_cer += c
             num_tokens += len(reference.split())
             num_chars += len(reference)
+            if want_nbest:
+                oracle_wer += min(decoder.wer(alt, reference) for alt in decoded[i])
+                oracle_cer += min(decoder.cer(alt, reference) for alt in decoded[i])
+            if args.nbest_path:
+                if nbest > 1:
+                    fields = zip(decoded[i], decoder.last_nbest_scores[i], decoder.last_nbest_ctc_log_probs[i],
+                                 decoder.last_nbest_posteriors[i])
+                else:                               # the 1-best entries: one alternative, the whole weight unless impossible
+                    s = decoder.last_scores[i]
+                    fields = [(transcript, s, decoder.last_ctc_log_probs[i], 1.0 if s > float('-inf') else 0.0)]
+                nbest_lines.append(json.dumps({'reference': reference, 'alternatives': [
+                    {'text': t_, 'score': s_, 'ctc_logp': c_, 'posterior': p_} for t_, s_, c_, p_ in fields]}))
             if args.verbose:
                 print('Ref: {}\nHyp: {}\nWER: {}\t CER: {}\n'.format(reference.lower(), transcript.lower(),
                                                                       w / max(1, len(reference.split())),
@@ -102,6 +129,12 @@ def main(argv=None):
     if decoder is not None:
         print('Test Summary \tAverage WER {wer:.3f}\tAverage CER {cer:.3f}\t'.format(
             wer=100.0 * total_wer / max(1, num_tokens), cer=100.0 * total_cer / max(1, num_chars)))
+        if args.nbest is not None:
+            print('Oracle Summary \tN-best {n}\tOracle WER {wer:.3f}\tOracle CER {cer:.3f}\t'.format(
+                n=nbest, wer=100.0 * oracle_wer / max(1, num_tokens), cer=100.0 * oracle_cer / max(1, num_chars)))
+        if args.nbest_path:
+            with open(args.nbest_path, 'w') as f:
+                f.write(''.join(line + '\n' for line in nbest_lines))
     else:
         np.save(args.output_path, np.asarray(output_data, dtype=object), allow_pickle=True)
 

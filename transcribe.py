@@ -4,7 +4,7 @@
     python transcribe.py --model-path CKPT (--audio A.wav [B.wav ...] | --manifest M.csv [--data-dir DIR])
                          --output-path OUT.jsonl [--batch-size 32] [--decoder greedy|beam] [--beam-width W]
                          [--lm-path F --lm-unit U --alpha A --beta B] [--beam-device] [--resample]
-                         [--hotword PHRASE ...] [--hotwords FILE] [--hotword-weight W]
+                         [--hotword PHRASE ...] [--hotwords FILE] [--hotword-weight W] [--nbest N]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
 
@@ -20,7 +20,11 @@ test.py's.  Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by 
 16 kHz mono on the device (``codes.transforms.Resample``, ``ds2_resample``) before it is segmented; the record gains
 ``source_rate`` and ``source_channels``, and ``duration`` and all times refer to the 16 kHz samples.  ``--hotword`` /
 ``--hotwords`` boost phrases in ``--decoder beam`` (``codes.bias.PhraseBooster``, the device search); the record gains
-``hotwords``, the phrases as normalised."""
+``hotwords``, the phrases as normalised.  ``--nbest N`` (``--decoder beam``, the device search; 1..``--beam-width``): the
+record gains ``nbest`` and every segment ``alternatives``, a list of ``{text, score, posterior}``, best first, element 0
+being the segment's ``text``; ``words`` and all times stay those of the 1-best, and ``posterior`` is the weight of an
+alternative among the ones returned under the fused score (``codes.decoder.DeviceBeamCTCDecoder``), not a calibrated
+probability."""
 import argparse
 import json
 import os
@@ -35,6 +39,7 @@ sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 
 from codes.align import ForcedAligner, group_words  # noqa: E402
 from codes.bias import add_hotword_arguments, booster_from_arguments, check_hotword_arguments  # noqa: E402
+from codes.decoder import add_nbest_arguments, check_nbest_arguments  # noqa: E402
 
 SAMPLE_RATE = 16000
 
@@ -110,9 +115,20 @@ def file_record(path, n_samples, stats, segments):
             'segments': segments}
 
 
-def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch_size, device='cuda'):
+def segment_alternatives(decoder, k, texts, nbest):
+    """``alternatives`` of utterance k of the decoder's last batch: ``[{text, score, posterior}]``, best first."""
+    if nbest > 1:
+        scores, post = decoder.last_nbest_scores[k], decoder.last_nbest_posteriors[k]
+    else:                                                   # the 1-best entry: the whole weight, unless nothing is possible
+        scores = [decoder.last_scores[k]]
+        post = [1.0 if scores[0] > float('-inf') else 0.0]
+    return [{'text': t, 'score': s, 'posterior': p} for t, s, p in zip(texts, scores, post)]
+
+
+def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch_size, device='cuda', nbest=None):
     """``samples``: 1-D int16 numpy array or tensor of one recording -> its JSON record.  One upload, one segmentation and
-    one int16 -> float conversion of the whole buffer; every segment is a slice of that buffer."""
+    one int16 -> float conversion of the whole buffer; every segment is a slice of that buffer.  ``nbest``: the N of
+    ``--nbest`` (a ``DeviceBeamCTCDecoder(nbest=N)``); every segment then gains ``alternatives``."""
     from ds2hip import ops
     pcm = torch.as_tensor(samples)
     n = int(pcm.numel())
@@ -129,6 +145,8 @@ def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch
             decoded, offsets = decoder.decode(out, sizes)
             for k, i in enumerate(group):
                 entries[i] = segment_record(blocks[i][0], blocks[i][1], decoded[k][0], offsets[k][0].tolist())
+                if nbest is not None:
+                    entries[i]['alternatives'] = segment_alternatives(decoder, k, decoded[k], nbest)
     return file_record(path, n, stats, entries)
 
 
@@ -153,6 +171,7 @@ def main(argv=None):
     p.add_argument('--beam-device', action='store_true',
                    help='run --decoder beam as one batched device launch (implied by --lm-path)')
     add_hotword_arguments(p)
+    add_nbest_arguments(p)
     p.add_argument('--max-segment', default=15.0, type=float, help='longest segment in seconds (default: 15)')
     p.add_argument('--min-speech', default=0.25, type=float, help='shorter speech is dropped, seconds (default: 0.25)')
     p.add_argument('--min-silence', default=0.3, type=float, help='shorter gaps are closed, seconds (default: 0.3)')
@@ -166,6 +185,7 @@ def main(argv=None):
     if args.lm_path and args.decoder != 'beam':
         p.error('--lm-path needs --decoder beam: only the beam search can fuse a language model')
     hotwords = check_hotword_arguments(p, args)
+    nbest = check_nbest_arguments(p, args)
     if args.batch_size < 1:
         p.error('--batch-size must be at least 1')
 
@@ -203,14 +223,14 @@ def main(argv=None):
     target_t = target_t[0]
     if args.decoder == 'greedy':
         decoder = GreedyDecoder(target_t.label_encoder)
-    elif args.lm_path or args.beam_device or hotwords:
+    elif args.lm_path or args.beam_device or hotwords or args.nbest is not None:
         lm = None
         if args.lm_path:
             from codes.lm import NGramLM
             lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
         booster = booster_from_arguments('transcribe.py', args, target_t) if hotwords else None
         decoder = DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                       beta=args.beta, booster=booster)
+                                       beta=args.beta, booster=booster, nbest=nbest)
     else:
         decoder = BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
@@ -223,8 +243,11 @@ def main(argv=None):
                 samples, source = source_samples(path, args.resample, resampler)
             except ValueError as e:
                 raise SystemExit('transcribe.py: ' + str(e))
-            rec = transcribe_samples(name, samples, model, frontend, decoder, segmenter, args.batch_size)
+            rec = transcribe_samples(name, samples, model, frontend, decoder, segmenter, args.batch_size,
+                                     nbest=args.nbest)
             rec.update(source)
+            if args.nbest is not None:
+                rec['nbest'] = nbest
             if hotwords:
                 rec['hotwords'] = list(decoder.booster.keywords)
             n_seg += len(rec['segments'])
