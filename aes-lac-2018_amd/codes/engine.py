@@ -22,6 +22,11 @@ carries per-task lists (``None`` for an absent task), the step loss is sum_i w_i
 task i's CTC gradient is scaled by w_i / B_i, and the infinite-loss rule applies PER TASK: an infeasible task contributes 0
 and a zero gradient, the others are unaffected (the reference sanitises each task's loss on its own, ``:68-76``).  The same
 single readback carries every task's cost sum.
+
+MWER fine-tuning (``mwer``, the optional ``training.mwer`` block; not in the reference): the step's loss becomes the expected
+word (or character) errors over the device N-best list plus ``ctc_weight`` times the CTC cost
+(``codes.ctc.mwer_costs_and_grad``), with the same 1/B and the same whole-batch inf rule; the reported loss is the batch mean,
+``last_expected_risk`` the batch mean of the expected risk.  Single-task only.  Without the block nothing of it runs.
 """
 import logging
 import os
@@ -32,7 +37,7 @@ import torch.distributed as dist
 
 from ds2hip import ops
 
-from .ctc import ctc_costs_and_grad
+from .ctc import MWERLoss, ctc_costs_and_grad, mwer_costs_and_grad
 from .data import TaskCounts, split_tasks, wait_ready
 
 LOG = logging.getLogger('aes-lac-2018')
@@ -85,9 +90,12 @@ class PendingLoss(object):
 
 class Trainer(object):
     def __init__(self, model, optimizer, criterion=None, device='cuda', max_norm=400, skip_n=0, frontend=None,
-                 overlap_allreduce=True, task_weights=None):
+                 overlap_allreduce=True, task_weights=None, mwer=None, space_id=None):
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
         self.task_weights = None if task_weights is None else [float(w) for w in task_weights]
+        self.mwer, self._exp_risk = None, None
+        if mwer is not None:
+            self._bind_mwer(mwer, space_id)
         self.device = torch.device(device)
         self.max_norm = max_norm
         self.skip_n = skip_n
@@ -127,6 +135,37 @@ class Trainer(object):
         torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         small = [torch.empty(1 << 20, dtype=torch.uint8, device=self.device) for _ in range(2 * int(small_blocks))]
         del small
+
+    # ---------------------------------------------------------------- MWER fine-tuning (the optional ``training.mwer`` block)
+    def _bind_mwer(self, mwer, space_id):
+        """``mwer``: the keywords of ``codes.ctc.mwer_costs_and_grad`` (nbest, beam_width, ctc_weight, risk; ``{}`` is all
+        defaults).  With it the step minimises the expected word (or character) errors over the device N-best list plus
+        ctc_weight * CTC instead of the CTC cost alone; validation is unchanged."""
+        if self.task_weights is not None:
+            raise ValueError('mwer with a multi-task model: MWER training covers one classifier (each head would need its '
+                             'own N-best search, risks and space label); train the heads with CTC')
+        space_id = -1 if space_id is None else int(space_id)
+        if mwer.get('risk', 'word') == 'word' and space_id < 0:
+            raise ValueError('mwer: risk = \'word\' needs space_id, the label of the space; this alphabet has none '
+                             '(use risk = \'char\')')
+        self.mwer, self.space_id = dict(mwer), space_id
+        self._mwer_loss = MWERLoss(space_id, **self.mwer)              # the autograd path's criterion; refuses unknown keys
+
+    def _mwer_loss_fn(self, targets, input_percentages, target_sizes, bsz):
+        """The fused step's ``acts -> (loss_b, d_acts)`` with the block: the same 1/B and whole-batch inf rule as the CTC step."""
+        def loss_fn(acts):
+            out_sizes = sanitize_inputs(acts.shape[0], input_percentages)
+            loss, d_acts, info = mwer_costs_and_grad(acts, targets, out_sizes, target_sizes, self.space_id,
+                                                     grad_scale=1.0 / bsz, zero_batch_if_inf=True, **self.mwer)
+            self._exp_risk = info['exp_risk']
+            return loss, d_acts
+        return loss_fn
+
+    @property
+    def last_expected_risk(self):
+        """Batch mean of the expected risk (word or character errors per utterance) of the last MWER step; None before the
+        first one and without the block.  Read lazily: the device tensor is fetched when this is looked at."""
+        return None if self._exp_risk is None else float(self._exp_risk.mean().item())
 
     # ---------------------------------------------------------------- optimizer plumbing
     def _fused_ok(self):
@@ -225,6 +264,8 @@ class Trainer(object):
                                                zero_batch_if_inf=True)      # codes/engine.py:24-30
             return costs, d_acts
 
+        if self.mwer is not None:
+            loss_fn = self._mwer_loss_fn(targets, input_percentages, target_sizes, bsz)
         hook = self._bucket_hook() if self.overlap else None
         costs, _ = self._forward_backward(inputs, loss_fn, hook)
         return self._finish_step([costs], bsz, None, defer)
@@ -375,7 +416,10 @@ class Trainer(object):
         """Reference-shaped step through autograd, for optimizers the fused kernel does not cover."""
         out = self.model(inputs)                                        # (B,T,A)
         out_sizes = sanitize_inputs(out.shape[1], input_percentages)
-        loss = self.criterion(out.transpose(0, 1), targets, out_sizes, target_sizes) / inputs.shape[0]
+        criterion = self.criterion if self.mwer is None else self._mwer_loss
+        loss = criterion(out.transpose(0, 1), targets, out_sizes, target_sizes) / inputs.shape[0]
+        if self.mwer is not None:
+            self._exp_risk = self._mwer_loss.last_info['exp_risk']
         loss = loss.sum()
         is_inf = float(loss.item()) in (float('inf'), float('-inf'))
         if is_inf:                                   # codes/engine.py:27-30: 0 * loss -> a zero gradient, the step still runs
@@ -582,7 +626,7 @@ def create_trainer(model, optimizer, criterion, device, **kwargs):
         crit = criterion[0] if isinstance(criterion, (list, tuple)) else criterion
     return Trainer(model, optimizer, crit, device, max_norm=kwargs.get('max_norm', 400),
                    skip_n=kwargs.get('skip_n', 0), frontend=kwargs.get('frontend', None),
-                   task_weights=weights if multi else None)
+                   task_weights=weights if multi else None, mwer=kwargs.get('mwer'), space_id=kwargs.get('space_id'))
 
 
 def create_evaluator(model, metrics=None, device='cuda', decoder=None):

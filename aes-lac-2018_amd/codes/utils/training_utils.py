@@ -3,7 +3,7 @@
 Config schema (unchanged): ``model{name, langs, freeze_layers, map_fc, params}``,
 ``training{num_epochs, batch_size, max_norm, augment, finetune}``, ``optimizer{name, params, per_layer_lr}``,
 ``scheduler{name, params}``.  Additions: ``training.audio_scale`` (``audio_scale``) and the optional block
-``training.noise{path, noise_levels, prob}`` (``get_noise``), ``training.reverb{path, prob, ...}`` (``get_reverb``), ``training.speed{factors, prob}`` (``get_speed``) and ``training.spec_augment{...}`` (``get_spec_augment``).  Broken branches of the reference are implemented to their evident intent
+``training.noise{path, noise_levels, prob}`` (``get_noise``), ``training.reverb{path, prob, ...}`` (``get_reverb``), ``training.speed{factors, prob}`` (``get_speed``) and ``training.spec_augment{...}`` (``get_spec_augment``), and ``training.mwer{nbest, beam_width, ctc_weight, risk}`` (``get_mwer``).  Broken branches of the reference are implemented to their evident intent
 (SURVEY.md section 4): ``langs[0]`` is the fine-tune target language, the new FC layer's *weight* is
 normally initialised.
 """
@@ -147,6 +147,48 @@ def get_spec_augment(config):
         raise ValueError('training.spec_augment: unknown key(s) %s; it takes %s' % (', '.join(unknown),
                                                                                    ', '.join(SPEC_AUGMENT_KEYS)))
     return transforms.SpecAugment(**{k: block[k] for k in SPEC_AUGMENT_KEYS if k in block})
+
+
+MWER_KEYS = ('nbest', 'beam_width', 'ctc_weight', 'risk')
+MWER_DEFAULTS = {'nbest': 4, 'beam_width': 8, 'ctc_weight': 0.01, 'risk': 'word'}
+MWER_MAX_BEAM = 128                      # DS2_MWER_MAX_NBEST of include/ds2hip.h
+
+
+def get_mwer(config, labels=None):
+    """``training.mwer`` of the JSON config (an addition to the reference's schema): ``{"nbest": 4, "beam_width": 8,
+    "ctc_weight": 0.01, "risk": "word"}`` -> the block with its defaults filled in, the keywords of
+    ``codes.ctc.mwer_costs_and_grad`` (None without the block; ``{}`` is all defaults).  Refused by name when the config is
+    loaded: an unknown key, ``beam_width`` outside 1..128, ``nbest`` outside 1..beam_width, a negative ``ctc_weight``, a
+    ``risk`` other than word / char, a multi-task config, and -- with ``labels``, the alphabet as a list -- ``risk = word``
+    on an alphabet without a space label.  The block is saved with the checkpoint's ``args``; nothing reads it at test time."""
+    training = config.get('training', {}) if hasattr(config, 'get') else {}
+    block = (training or {}).get('mwer', None)
+    if block is None:
+        return None
+    unknown = sorted(set(block) - set(MWER_KEYS))
+    if unknown:
+        raise ValueError('training.mwer: unknown key(s) %s; it takes %s' % (', '.join(unknown), ', '.join(MWER_KEYS)))
+    out = dict(MWER_DEFAULTS)
+    out.update({k: block[k] for k in MWER_KEYS if k in block})
+    for key in ('nbest', 'beam_width'):
+        if isinstance(out[key], bool) or not isinstance(out[key], int):
+            raise ValueError('training.mwer: %s must be an integer, got %r' % (key, out[key]))
+    if not 1 <= out['beam_width'] <= MWER_MAX_BEAM:
+        raise ValueError('training.mwer: beam_width %d is outside 1..%d' % (out['beam_width'], MWER_MAX_BEAM))
+    if not 1 <= out['nbest'] <= out['beam_width']:
+        raise ValueError('training.mwer: nbest %d is outside 1..beam_width = %d' % (out['nbest'], out['beam_width']))
+    if isinstance(out['ctc_weight'], bool) or not isinstance(out['ctc_weight'], (int, float)) or \
+            not 0 <= out['ctc_weight'] < float('inf'):
+        raise ValueError('training.mwer: ctc_weight must be a finite number >= 0, got %r' % (out['ctc_weight'],))
+    if out['risk'] not in ('word', 'char'):
+        raise ValueError('training.mwer: risk must be "word" or "char", got %r' % (out['risk'],))
+    langs = (config.get('model', None) or {}).get('langs', None)
+    if isinstance(langs, (tuple, set, list)) and len(langs) > 1:
+        raise ValueError('training.mwer in a multi-task config (model.langs = %s): MWER training covers one classifier'
+                         % list(langs))
+    if labels is not None and out['risk'] == 'word' and ' ' not in list(labels):
+        raise ValueError('training.mwer: risk = "word" needs an alphabet with a space label; use risk = "char"')
+    return out
 
 
 def is_multitask(config):

@@ -79,6 +79,9 @@ SIGNATURES = {
     'ds2_greedy_collapse': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ds2_ctc_ws_bytes': (_Z, [_I, _I, _I, _I]),
     'ds2_ctc_loss_grad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    'ds2_ctc_mwer_ws_bytes': (_Z, [_I, _I, _I, _I, _I]),
+    'ds2_ctc_mwer_grad': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P,
+                               _P, _P]),
     'ds2_sumsq_ws_bytes': (_Z, [_Z]),
     'ds2_sumsq': (_I, [_P, _Z, _P, _P, _P]),
     'ds2_clip_sgd_nesterov': (_I, [_P, _P, _P, _Z, _P, _F, _F, _F, _F, _I, _P]),
@@ -115,6 +118,7 @@ ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3           # DS2_ERR_* of inclu
 ALIGN_BAND_MIN, ALIGN_BAND_MAX = 64, 8192                   # DS2_ALIGN_BAND_* of include/ds2hip.h (ds2_ctc_align_banded)
 KWS_MAX_LEN = 64                                            # DS2_KWS_MAX_LEN of include/ds2hip.h (ds2_ctc_keyword_search)
 BIAS_MAX_LEN, BIAS_MAX_PHRASES, BIAS_MAX_STATES = 64, 1024, 32768   # DS2_BIAS_MAX_* of include/ds2hip.h (phrase boosting)
+MWER_MAX_NBEST = 128                                       # DS2_MWER_MAX_NBEST of include/ds2hip.h (ds2_ctc_mwer_grad)
 EDIT_MAX_ITEMS = 2048                                      # DS2_EDIT_MAX_ITEMS of include/ds2hip.h (ds2_edit_stats)
 
 

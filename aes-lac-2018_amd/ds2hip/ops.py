@@ -1316,6 +1316,52 @@ def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_l
     return costs, grad
 
 
+MWER_MAX_NBEST = lib.MWER_MAX_NBEST     # DS2_MWER_MAX_NBEST of include/ds2hip.h
+
+
+def ctc_mwer_ws_bytes(t, bsz, a, nbest, max_label_len):
+    """Bytes of workspace ``ctc_mwer_grad`` needs (``ds2_ctc_mwer_ws_bytes``; 0 for sizes the entry refuses)."""
+    return int(lib.query('ds2_ctc_mwer_ws_bytes', int(t), int(bsz), int(a), int(nbest), int(max_label_len)))
+
+
+def ctc_mwer_grad(acts, act_lens, hyp, hyp_len, hyp_count, risk, ref, ref_offsets, ref_lens, max_label_len, ctc_weight=0.0,
+                  grad_scale=1.0, zero_batch_if_inf=False, ws=None):
+    """Minimum-word-error-rate loss terms and gradient of N-best lists in one call on the current stream
+    (``ds2_ctc_mwer_grad``; include/ds2hip.h "MWER" has the definition and the rules).  acts (T,B,A) fp32 un-normalised;
+    hyp (B,N,stride), hyp_len (B,N), hyp_count (B,) int32 as ``ctc_beam_search_nbest`` returns them; risk (B,N) fp32; flat
+    ref, ref_offsets (B,), ref_lens (B,), act_lens (B,) int32; all on the device.  ``ws``: a uint8 device tensor of at least
+    ``ctc_mwer_ws_bytes`` bytes, or None to allocate one.  Returns the device tensors (ref_costs (B,), hyp_costs (B,N),
+    posterior (B,N), exp_risk (B,), dropped (B,) int32, grad (T,B,A)).  Nothing waits on the stream."""
+    _require_device('ctc_mwer_grad', torch.float32, acts=acts, risk=risk)
+    _require_device('ctc_mwer_grad', torch.int32, act_lens=act_lens, hyp=hyp, hyp_len=hyp_len, hyp_count=hyp_count, ref=ref,
+                    ref_offsets=ref_offsets, ref_lens=ref_lens)
+    if acts.dim() != 3 or hyp.dim() != 3:
+        raise RuntimeError('ctc_mwer_grad: acts must be (T,B,A) and hyp (B,N,stride)')
+    t, bsz, a = acts.shape
+    n, stride = int(hyp.shape[1]), int(hyp.shape[2])
+    if int(hyp.shape[0]) != bsz or tuple(hyp_len.shape) != (bsz, n) or tuple(risk.shape) != (bsz, n):
+        raise RuntimeError('ctc_mwer_grad: hyp (B,N,stride), hyp_len (B,N) and risk (B,N) must agree with B = %d of acts' % bsz)
+    for name, x in (('act_lens', act_lens), ('hyp_count', hyp_count), ('ref_offsets', ref_offsets), ('ref_lens', ref_lens)):
+        if int(x.numel()) != bsz:
+            raise RuntimeError('ctc_mwer_grad: %s must have B = %d entries' % (name, bsz))
+    max_label_len = int(max_label_len)
+    if ws is None:
+        ws = _bytes_ws(max(ctc_mwer_ws_bytes(t, bsz, a, n, max_label_len), 16), acts)
+    elif ws.numel() * ws.element_size() < ctc_mwer_ws_bytes(t, bsz, a, n, max_label_len):
+        raise RuntimeError('ctc_mwer_grad: ws holds %d bytes, %d are needed'
+                           % (ws.numel() * ws.element_size(), ctc_mwer_ws_bytes(t, bsz, a, n, max_label_len)))
+    ref_costs = _empty((bsz,), acts)
+    hyp_costs = _empty((bsz, n), acts)
+    posterior = _empty((bsz, n), acts)
+    exp_risk = _empty((bsz,), acts)
+    dropped = _empty((bsz,), acts, torch.int32)
+    grad = torch.empty_like(acts)
+    lib.call('ds2_ctc_mwer_grad', acts, act_lens, t, bsz, a, hyp, hyp_len, hyp_count, n, stride, risk, ref, ref_offsets, ref_lens,
+             max_label_len, float(ctc_weight), float(grad_scale), int(bool(zero_batch_if_inf)), ref_costs, hyp_costs, posterior,
+             exp_risk, dropped, grad, ws)
+    return ref_costs, hyp_costs, posterior, exp_risk, dropped, grad
+
+
 # ----------------------------------------------------------------------------- optimiser
 def sumsq(x, out=None):
     if out is None:

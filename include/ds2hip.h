@@ -798,6 +798,47 @@ int ds2_ctc_loss_grad(const float* acts, const int32_t* labels, const int32_t* l
                       int max_label_len, float grad_scale, int zero_batch_if_inf, float* costs,
                       float* grad, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ MWER (csrc/ctc_mwer.hip)
+ * Not in the reference.  Minimum-word-error-rate loss and gradient from N-best lists (Prabhavalkar et al. 2018; Shannon 2017):
+ * utterance b owns the label rows n = 0 .. hyp_count[b] - 1 of hyp (B,N,hyp_stride) with lengths hyp_len (B,N), as
+ * ds2_ctc_beam_search_nbest writes them, a risk W_n = risk[b][n] per row (its word or character distance to the reference,
+ * ds2_edit_stats), and a reference given as for ds2_ctc_loss_grad.  acts (T,B,A) un-normalised, blank 0.  With
+ *   c_n   = -log P(y_n | acts[:act_lens[b], b]), the EXACT CTC cost of row n by forward-backward (not the search's pruned
+ *           ctc_logp), c_ref the reference's,
+ *   P_n   = exp(-c_n) / sum_m exp(-c_m)   over the rows of finite cost, in float64,
+ *   E_b   = sum_n P_n W_n                 the expected risk,
+ *   loss_b = E_b + ctc_weight * c_ref     (left to the caller: exp_risk and ref_costs are outputs),
+ *   grad  = grad_scale * sum_b ( sum_n w_n * dc_n/dacts + ctc_weight * dc_ref/dacts ),   w_n = -P_n (W_n - E_b),
+ * where dc/dacts = softmax - occupancy as in ds2_ctc_loss_grad.  The rules:
+ *   - a row of infinite cost has P = 0 and no gradient; its risk is not read;
+ *   - a row longer than max_label_len (or than hyp_stride, or of negative length) is dropped: it counts as a row of infinite
+ *     cost and dropped[b] counts it;
+ *   - an utterance with no finite row has E = 0 and only its CTC term;
+ *   - an utterance whose reference is infeasible (or longer than max_label_len) has ref_costs = +inf and contributes no gradient
+ *     at all, neither term; its exp_risk is still reported;
+ *   - zero_batch_if_inf = 1 applies the training step's rule of ds2_ctc_loss_grad: a reference of infinite cost zeroes the whole
+ *     batch's gradient;
+ *   - rows at or past hyp_count[b] are never read (labels, lengths and risks there may hold anything); their hyp_costs is +inf
+ *     and their posterior 0;
+ *   - frames at or past act_lens[b] get zero gradient, and what acts holds there (NaN included) is harmless;
+ *   - adding a constant to every W_n of an utterance leaves the gradient unchanged up to rounding (sum_n w_n = 0).
+ * Risks are expected within +-2^15 (they are label counts); the weighted occupancies are summed in 64-bit fixed point of 2^-44
+ * units, so the result is bit-identical from run to run and does not depend on what ws held.
+ * Outputs: ref_costs (B), hyp_costs (B,N), posterior (B,N) = P_n, exp_risk (B) = E_b, dropped (B), grad (T,B,A).
+ * 1 <= N <= DS2_MWER_MAX_NBEST; max_label_len <= 511 and A <= 256 as for ds2_ctc_loss_grad; ctc_weight >= 0;
+ * ws >= ds2_ctc_mwer_ws_bytes(T,B,A,N,max_label_len) bytes = two fp64 planes of (B (N+1), T, 2 max_label_len + 1) and small
+ * change; the query returns 0 for sizes the entry refuses.  DS2_ERR_ARG before any launch for a NULL pointer or a size outside
+ * these ranges.  Four launches on the stream (row log-sum-exp once per frame, one alpha / beta recursion per row and direction,
+ * the weights per utterance, the gradient per frame); no global atomics, and neither acts nor the gradient is replicated per row.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_MWER_MAX_NBEST 128
+size_t ds2_ctc_mwer_ws_bytes(int T, int B, int A, int N, int max_label_len);
+int ds2_ctc_mwer_grad(const float* acts, const int32_t* act_lens, int T, int B, int A, const int32_t* hyp,
+                      const int32_t* hyp_len, const int32_t* hyp_count, int N, int hyp_stride, const float* risk,
+                      const int32_t* ref, const int32_t* ref_offsets, const int32_t* ref_lens, int max_label_len,
+                      float ctc_weight, float grad_scale, int zero_batch_if_inf, float* ref_costs, float* hyp_costs,
+                      float* posterior, float* exp_risk, int32_t* dropped, float* grad, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ optimiser
  * clip_grad_norm_(params, max_norm) + SGD(momentum, nesterov) (codes/engine.py:87-90) over ONE
  * flat fp32 buffer of n elements (the model keeps params / grads / momentum flat).

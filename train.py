@@ -132,6 +132,7 @@ def main(argv=None):
         args.config = expand_values(args.config, **args)
     tu.check_multitask_config(args.config)
     tu.get_speed(args.config)                        # (a bad training.speed block is refused here, when the config is loaded)
+    tu.get_mwer(args.config)                         # (and a bad training.mwer block; the alphabet is checked below)
     multi = tu.is_multitask(args.config)
     out_dir = os.path.join(args.save_folder, args.config.model.name)
     os.makedirs(out_dir, exist_ok=True)
@@ -185,8 +186,12 @@ def main(argv=None):
             ld.frontend = frontend
     steps_per_epoch = max(1, len(train_loader))
     skip_n = int(start_iteration % steps_per_epoch)               # train.py:198-200
+    classes = [str(c) for c in target_t[0].label_encoder.classes_.tolist()]
+    mwer = tu.get_mwer(args.config, labels=classes)                # (risk = word on an alphabet without a space is refused)
+    if mwer is not None:
+        LOG.info('MWER fine-tuning: {}'.format(mwer))
     trainer = create_trainer(model, optimizer, criterion, device, skip_n=skip_n, frontend=frontend,
-                             **args.config.training)
+                             space_id=classes.index(' ') if ' ' in classes else -1, **args.config.training)
     evaluator = create_evaluator(model, None, device, decoder=decoder)
     best = BestCheckpoints(out_dir)
 
