@@ -46,6 +46,15 @@ def check_nbest_arguments(parser, args):
     return args.nbest
 
 
+def _device_sizes(probs, sizes):
+    """``sizes``, or without them the full length T for each of the B utterances of ``probs`` (B,T,A), as a contiguous
+    (B,) int32 tensor on the device of ``probs``."""
+    bsz, t, _ = probs.shape
+    if sizes is None:
+        return torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
+    return torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+
+
 class Decoder(object):
     def __init__(self, label_encoder, blank_index=0):
         if isinstance(label_encoder, str):
@@ -99,10 +108,7 @@ class GreedyDecoder(Decoder):
         bsz, t, a = probs.shape
         flat = probs.contiguous().float().view(bsz * t, a)
         best = ops.argmax_rows(flat, bsz * t, a).view(bsz, t)
-        if sizes is None:
-            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
-        else:
-            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32)
+        sizes_d = _device_sizes(probs, sizes)
         ids, offs, lens = ops.greedy_collapse(best, sizes_d, self.blank_index)
         ids, offs, lens = ids.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
         strings = [[self._to_string(ids[b, :lens[b]])] for b in range(bsz)]
@@ -116,10 +122,7 @@ class GreedyDecoder(Decoder):
             raise RuntimeError('GreedyDecoder.decode_labels runs on device tensors only')
         bsz, t, a = probs.shape
         best = ops.argmax_rows(probs.contiguous().float().view(bsz * t, a), bsz * t, a).view(bsz, t)
-        if sizes is None:
-            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
-        else:
-            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32)
+        sizes_d = _device_sizes(probs, sizes)
         ids, _, lens = ops.greedy_collapse(best, sizes_d, self.blank_index)
         return ids, lens
 
@@ -262,13 +265,10 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     def decode(self, probs, sizes=None):
         if not probs.is_cuda:
             raise RuntimeError('DeviceBeamCTCDecoder.decode runs on device tensors only')
-        bsz, t, _ = probs.shape
-        if sizes is None:
-            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
-        else:
-            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
+        sizes_d = _device_sizes(probs, sizes)
         if self.nbest > 1:
             return self._decode_nbest(probs, sizes_d)
+        bsz = probs.shape[0]
         labels, offs, lens, score, ctc, bias = self._search(probs, sizes_d)
         labels, offs, lens = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
         if bias is not None:
@@ -286,12 +286,7 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         (B,) int32 DEVICE tensor of the counts."""
         if not probs.is_cuda:
             raise RuntimeError('DeviceBeamCTCDecoder.decode_labels runs on device tensors only')
-        bsz, t, _ = probs.shape
-        if sizes is None:
-            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
-        else:
-            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
-        labels, _, lens, _, _, bias = self._search(probs, sizes_d)
+        labels, _, lens, _, _, bias = self._search(probs, _device_sizes(probs, sizes))
         if bias is not None:
             self.last_bias_counts = bias
         return labels, lens
@@ -303,10 +298,5 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
         stream and no ``last_*`` field is touched."""
         if not probs.is_cuda:
             raise RuntimeError('DeviceBeamCTCDecoder.decode_labels_nbest runs on device tensors only')
-        bsz, t, _ = probs.shape
-        if sizes is None:
-            sizes_d = torch.full((bsz,), t, dtype=torch.int32, device=probs.device)
-        else:
-            sizes_d = torch.as_tensor(sizes).to(device=probs.device, dtype=torch.int32).contiguous()
-        labels, _, lens, _, _, _, count = self._search_nbest(probs, sizes_d)
+        labels, _, lens, _, _, _, count = self._search_nbest(probs, _device_sizes(probs, sizes))
         return labels, lens, count

@@ -21,6 +21,10 @@
 // After the last frame the end-of-utterance LM terms are added, the best entry is picked (ties -> lower slot) and its
 // node chain is followed back.  Merging compares 64-bit prefix hashes and lengths: two distinct prefixes of one beam
 // with equal hash and length (probability ~ W^2 / 2^64 per frame) would be merged wrongly.
+//
+// Host half (from ds2_ctc_beam_ws_bytes down): each extern "C" entry makes its own checks, fills a BeamCall by field name
+// and calls BeamCall::run(), which makes the checks all entries share and picks one of the five instantiations
+// <ROWS, BIAS, NBEST> in one place; beam_launch<...> sets that kernel's LDS attribute and launches it.
 #include "ds2_common.h"
 #include "ds2_hash.h"
 
@@ -609,16 +613,86 @@ namespace {
         }                                                             \
     } while (0)
 
-// the checks and the launch all entries share; R workgroups, utt == nullptr for the batch entry (R == B); bias != nullptr
-// for the phrase-boosting entry (its own arguments are checked there); nbest > 0 for the N-best entry (batch form only,
-// boosted or not: its outputs have nbest rows per utterance)
-int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B, int R, int T, int A, int blank,
-                int beam_width, int log_input, const void* ngram_table, int ngram_cap, const void* word_table, int word_cap,
-                int order, int unit, int bos_id, int eos_id, int unk_id, int space_id, float alpha, float beta,
-                float oov_logp, const int32_t* utt, const float* alpha_r, const float* beta_r, void* ws, size_t ws_bytes,
-                int32_t* out_labels, int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
-                void* stream, const BiasArgs* bias = nullptr, int32_t* out_bias = nullptr, int nbest = 0,
-                int32_t* out_count = nullptr) {
+// the 13 LM values every entry receives, in the ABI's order and under its names (the refusal messages quote them): an
+// entry hands them over as one braced list
+struct BeamLm {
+    const void* ngram_table;
+    int ngram_cap;
+    const void* word_table;
+    int word_cap, order, unit, bos_id, eos_id, unk_id, space_id;
+    float alpha, beta, oov_logp;      // _rows has no scalar weights: it gives 0, 0
+};
+
+// One search as its entry point received it (host only): the entry makes its own checks, fills what it has by name --
+// the rest stays zero -- and calls run().
+struct BeamCall {
+    const char* fn;                   // the entry's name, for messages
+    const float* probs;
+    const int32_t* sizes;
+    int B, R, T, A, blank, beam_width, log_input;   // R workgroups: B but for _rows
+    BeamLm lm;                        // as given, unchecked
+    const int32_t* utt;               // _rows only: the utterance and the LM weights of each row
+    const float *alpha_r, *beta_r;
+    void* ws;
+    size_t ws_bytes;
+    int32_t *out_labels, *out_offsets, *out_len;
+    float *out_score, *out_ctc_logp;
+    BiasArgs bias;                    // phrase boosting if bias.trans, set with out_bias by check_bias
+    int32_t* out_bias;
+    int nbest;                        // > 0: the outputs have nbest rows per utterance (batch form only)
+    int32_t* out_count;
+    void* stream;
+
+    int run() const;                  // the checks all entries share, then the launch
+};
+
+// the context-graph arguments of _bias and _nbest -> c.bias and c.out_bias, or false with the error set (DS2_ERR_ARG);
+// null_text is the entry's wording
+bool check_bias(BeamCall& c, const char* null_text, const int32_t* bias_trans, const int32_t* bias_final, int bias_states,
+                float bias_weight, int32_t* out_bias) {
+    if (bias_states < 1 || bias_states > DS2_BIAS_MAX_STATES) {
+        ds2_set_error("%s: %d context-graph states are outside 1..%d", c.fn, bias_states, DS2_BIAS_MAX_STATES);
+        return false;
+    }
+    if (!(bias_weight - bias_weight == 0.f)) {
+        ds2_set_error("%s: the weight %g is not finite", c.fn, (double)bias_weight);
+        return false;
+    }
+    if (!bias_trans || !bias_final || !out_bias) {
+        ds2_set_error("%s: %s", c.fn, null_text);
+        return false;
+    }
+    c.bias = BiasArgs{bias_trans, bias_final, bias_states, (double)bias_weight};
+    c.out_bias = out_bias;
+    return true;
+}
+
+// one instantiation: the kernel whose LDS attribute is raised is by construction the kernel that is launched
+template <bool ROWS, bool BIAS, bool NBEST>
+int beam_launch(const BeamCall& c, const LmArgs& lm) {
+    const auto kern = &ctc_beam_kernel<ROWS, BIAS, NBEST>;
+    const size_t dyn = (size_t)c.beam_width * c.A * sizeof(uint64_t);
+    const size_t fixed = sizeof(BeamLds) + (BIAS ? 2 * MAX_W * sizeof(int) : 0);
+    if (dyn + fixed > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+        ds2_set_error("%s: %zu bytes of LDS are not available", c.fn, dyn + fixed);
+        return DS2_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(kern, dim3(c.R), dim3(BEAM_THREADS), dyn, (hipStream_t)c.stream, c.probs, c.sizes, c.B, c.T, c.A,
+                       c.blank, c.beam_width, c.log_input, lm, c.utt, c.alpha_r, c.beta_r, (BeamNode*)c.ws, c.out_labels,
+                       c.out_offsets, c.out_len, c.out_score, c.out_ctc_logp, BIAS ? c.bias : BiasArgs{},
+                       BIAS ? c.out_bias : nullptr, NBEST ? c.nbest : 0, NBEST ? c.out_count : nullptr);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) {
+        ds2_set_error("%s: launch failed: %s", c.fn, hipGetErrorString(e_));
+        return DS2_ERR_LAUNCH;
+    }
+    return DS2_OK;
+}
+
+int BeamCall::run() const {
+    const auto& [ngram_table, ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta,
+                 oov_logp] = lm;
     if (beam_width < 1 || beam_width > MAX_W) {
         ds2_set_error("%s: beam_width %d is outside 1..%d", fn, beam_width, MAX_W);
         return DS2_ERR_ARG;
@@ -643,59 +717,33 @@ int beam_launch(const char* fn, const float* probs, const int32_t* sizes, int B,
         return DS2_ERR_ARG;
     }
     if (R == 0) return DS2_OK;
-    LmArgs lm{};
-    lm.ngram = (const uint64_t*)ngram_table;
-    lm.words = (const uint64_t*)word_table;
-    lm.ngram_cap = ngram_cap;
-    lm.word_cap = word_cap;
-    lm.order = unit ? order : 1;
-    lm.unit = unit;
-    lm.bos = bos_id;
-    lm.eos = eos_id;
-    lm.unk = unk_id;
-    lm.space = unit == 2 ? space_id : -1;
-    lm.alpha = unit ? (double)alpha : 0.0;
-    lm.beta = unit ? (double)beta : 0.0;
-    lm.oov = (double)oov_logp;
-    const size_t dyn = (size_t)beam_width * A * sizeof(uint64_t);
-    const void* kern = nbest ? (bias ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true, true>)
-                                     : reinterpret_cast<const void*>(&ctc_beam_kernel<false, false, true>))
-                       : bias  ? reinterpret_cast<const void*>(&ctc_beam_kernel<false, true>)
-                       : utt ? reinterpret_cast<const void*>(&ctc_beam_kernel<true, false>)
-                             : reinterpret_cast<const void*>(&ctc_beam_kernel<false, false>);
-    const size_t fixed = sizeof(BeamLds) + (bias ? 2 * MAX_W * sizeof(int) : 0);
-    if (dyn + fixed > 64 * 1024 &&
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
-        ds2_set_error("%s: %zu bytes of LDS are not available", fn, dyn + fixed);
-        return DS2_ERR_LAUNCH;
-    }
-    if (nbest && bias)
-        hipLaunchKernelGGL((ctc_beam_kernel<false, true, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs,
-                           sizes, B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias, nbest, out_count);
-    else if (nbest)
-        hipLaunchKernelGGL((ctc_beam_kernel<false, false, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs,
-                           sizes, B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, nbest, out_count);
-    else if (bias)
-        hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
-                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, *bias, out_bias, 0, nullptr);
-    else if (utt)
-        hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
-                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, 0, nullptr);
-    else
-        hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(R), dim3(BEAM_THREADS), dyn, (hipStream_t)stream, probs, sizes,
-                           B, T, A, blank, beam_width, log_input, lm, utt, alpha_r, beta_r, (BeamNode*)ws, out_labels,
-                           out_offsets, out_len, out_score, out_ctc_logp, BiasArgs{}, nullptr, 0, nullptr);
-    hipError_t e_ = hipGetLastError();
-    if (e_ != hipSuccess) {
-        ds2_set_error("%s: launch failed: %s", fn, hipGetErrorString(e_));
-        return DS2_ERR_LAUNCH;
-    }
-    return DS2_OK;
+    LmArgs dev{};
+    dev.ngram = (const uint64_t*)ngram_table;
+    dev.words = (const uint64_t*)word_table;
+    dev.ngram_cap = ngram_cap;
+    dev.word_cap = word_cap;
+    dev.order = unit ? order : 1;
+    dev.unit = unit;
+    dev.bos = bos_id;
+    dev.eos = eos_id;
+    dev.unk = unk_id;
+    dev.space = unit == 2 ? space_id : -1;
+    dev.alpha = unit ? (double)alpha : 0.0;
+    dev.beta = unit ? (double)beta : 0.0;
+    dev.oov = (double)oov_logp;
+    // the five instantiations <ROWS, BIAS, NBEST>: boosting and N-best exist in the batch form only
+    if (nbest) return bias.trans ? beam_launch<false, true, true>(*this, dev) : beam_launch<false, false, true>(*this, dev);
+    if (bias.trans) return beam_launch<false, true, false>(*this, dev);
+    return utt ? beam_launch<true, false, false>(*this, dev) : beam_launch<false, false, false>(*this, dev);
 }
+
+// what every entry receives under the same names; R = B until _rows says otherwise
+#define BEAM_CALL(c, name)                                                                                          \
+    BeamCall c{};                                                                                                   \
+    c.fn = name; c.probs = probs; c.sizes = sizes; c.B = c.R = B; c.T = T; c.A = A; c.blank = blank;                \
+    c.beam_width = beam_width; c.log_input = log_input; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;        \
+    c.out_labels = out_labels; c.out_offsets = out_offsets; c.out_len = out_len; c.out_score = out_score;           \
+    c.out_ctc_logp = out_ctc_logp
 
 }  // namespace
 
@@ -705,10 +753,9 @@ extern "C" int ds2_ctc_beam_search_batch(const float* probs, const int32_t* size
                                          int eos_id, int unk_id, int space_id, float alpha, float beta, float oov_logp,
                                          void* ws, size_t ws_bytes, int32_t* out_labels, int32_t* out_offsets,
                                          int32_t* out_len, float* out_score, float* out_ctc_logp, void* stream) {
-    return beam_launch("ds2_ctc_beam_search_batch", probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table,
-                       ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp,
-                       nullptr, nullptr, nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp,
-                       stream);
+    BEAM_CALL(c, "ds2_ctc_beam_search_batch");
+    c.lm = {ngram_table, ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp};
+    return c.run();
 }
 
 extern "C" int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes, const int32_t* utt, const float* alpha,
@@ -727,9 +774,13 @@ extern "C" int ds2_ctc_beam_search_rows(const float* probs, const int32_t* sizes
         ds2_set_error("ds2_ctc_beam_search_rows: utt%s must not be NULL", unit ? ", alpha and beta" : "");
         return DS2_ERR_ARG;
     }
-    return beam_launch("ds2_ctc_beam_search_rows", probs, sizes, B, R, T, A, blank, beam_width, log_input, ngram_table,
-                       ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, 0.f, 0.f, oov_logp, utt,
-                       alpha, beta, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream);
+    BEAM_CALL(c, "ds2_ctc_beam_search_rows");
+    c.R = R;
+    c.utt = utt;
+    c.alpha_r = alpha;
+    c.beta_r = beta;
+    c.lm = {ngram_table, ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, 0.f, 0.f, oov_logp};
+    return c.run();
 }
 
 extern "C" int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
@@ -740,24 +791,12 @@ extern "C" int ds2_ctc_beam_search_bias(const float* probs, const int32_t* sizes
                                         float bias_weight, void* ws, size_t ws_bytes, int32_t* out_labels,
                                         int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
                                         int32_t* out_bias, void* stream) {
-    const char* fn = "ds2_ctc_beam_search_bias";
-    if (bias_states < 1 || bias_states > DS2_BIAS_MAX_STATES) {
-        ds2_set_error("%s: %d context-graph states are outside 1..%d", fn, bias_states, DS2_BIAS_MAX_STATES);
+    BEAM_CALL(c, "ds2_ctc_beam_search_bias");
+    if (!check_bias(c, "bias_trans, bias_final and out_bias must not be NULL", bias_trans, bias_final, bias_states,
+                    bias_weight, out_bias))
         return DS2_ERR_ARG;
-    }
-    if (!(bias_weight - bias_weight == 0.f)) {
-        ds2_set_error("%s: the weight %g is not finite", fn, (double)bias_weight);
-        return DS2_ERR_ARG;
-    }
-    if (!bias_trans || !bias_final || !out_bias) {
-        ds2_set_error("%s: bias_trans, bias_final and out_bias must not be NULL", fn);
-        return DS2_ERR_ARG;
-    }
-    BiasArgs bias{bias_trans, bias_final, bias_states, (double)bias_weight};
-    return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
-                       word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
-                       nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, &bias,
-                       out_bias);
+    c.lm = {ngram_table, ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp};
+    return c.run();
 }
 
 extern "C" int ds2_ctc_beam_search_nbest(const float* probs, const int32_t* sizes, int B, int T, int A, int blank,
@@ -768,35 +807,21 @@ extern "C" int ds2_ctc_beam_search_nbest(const float* probs, const int32_t* size
                                          float bias_weight, int nbest, void* ws, size_t ws_bytes, int32_t* out_labels,
                                          int32_t* out_offsets, int32_t* out_len, float* out_score, float* out_ctc_logp,
                                          int32_t* out_bias, int32_t* out_count, void* stream) {
-    const char* fn = "ds2_ctc_beam_search_nbest";
+    BEAM_CALL(c, "ds2_ctc_beam_search_nbest");
     if (nbest < 1 || nbest > beam_width) {
-        ds2_set_error("%s: nbest %d is outside 1..beam_width = %d", fn, nbest, beam_width);
+        ds2_set_error("%s: nbest %d is outside 1..beam_width = %d", c.fn, nbest, beam_width);
         return DS2_ERR_ARG;
     }
     if (!out_count) {
-        ds2_set_error("%s: out_count must not be NULL", fn);
+        ds2_set_error("%s: out_count must not be NULL", c.fn);
         return DS2_ERR_ARG;
     }
-    if (!bias_trans)      // no boosting: the other bias arguments and out_bias are ignored
-        return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
-                           word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
-                           nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, nullptr,
-                           nullptr, nbest, out_count);
-    if (bias_states < 1 || bias_states > DS2_BIAS_MAX_STATES) {
-        ds2_set_error("%s: %d context-graph states are outside 1..%d", fn, bias_states, DS2_BIAS_MAX_STATES);
+    c.nbest = nbest;
+    c.out_count = out_count;
+    // without bias_trans there is no boosting: the other bias arguments and out_bias are ignored
+    if (bias_trans && !check_bias(c, "with bias_trans, bias_final and out_bias must not be NULL", bias_trans, bias_final,
+                                  bias_states, bias_weight, out_bias))
         return DS2_ERR_ARG;
-    }
-    if (!(bias_weight - bias_weight == 0.f)) {
-        ds2_set_error("%s: the weight %g is not finite", fn, (double)bias_weight);
-        return DS2_ERR_ARG;
-    }
-    if (!bias_final || !out_bias) {
-        ds2_set_error("%s: with bias_trans, bias_final and out_bias must not be NULL", fn);
-        return DS2_ERR_ARG;
-    }
-    BiasArgs bias{bias_trans, bias_final, bias_states, (double)bias_weight};
-    return beam_launch(fn, probs, sizes, B, B, T, A, blank, beam_width, log_input, ngram_table, ngram_cap, word_table,
-                       word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp, nullptr, nullptr,
-                       nullptr, ws, ws_bytes, out_labels, out_offsets, out_len, out_score, out_ctc_logp, stream, &bias,
-                       out_bias, nbest, out_count);
+    c.lm = {ngram_table, ngram_cap, word_table, word_cap, order, unit, bos_id, eos_id, unk_id, space_id, alpha, beta, oov_logp};
+    return c.run();
 }

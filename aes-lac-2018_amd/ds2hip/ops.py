@@ -1033,37 +1033,65 @@ def greedy_collapse(best, sizes, blank=0):
     return ids, offs, lens
 
 
-def ctc_beam_search(probs, sizes, beam_width, blank=0, log_input=False, lm=None, alpha=0.0, beta=0.0, space_id=-1):
-    """Batched CTC prefix beam search on the current stream (``ds2_ctc_beam_search_batch``).  probs (B,T,A) fp32 on the
-    device, sizes (B,) int32 on the device; ``lm`` an ``codes.lm.NGramLM`` or None.  Returns the device tensors
-    labels (B,T), offsets (B,T), lens (B,) int32 and score, ctc_logp (B,) fp32."""
-    bsz, t, a = probs.shape
-    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
-    ws = _bytes_ws(ws_bytes, probs)
-    labels = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    offsets = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    lens = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
-    score = _empty((bsz,), probs)
-    ctc = _empty((bsz,), probs)
-    if lm is None:
-        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
-    else:
-        tabs = lm.to(probs.device)
-        word = tabs.get('word')
-        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
-                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
-                   float(beta), float(lm.oov_logp))
-    lib.call('ds2_ctc_beam_search_batch', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
-             *lm_args, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc)
-    return labels, offsets, lens, score, ctc
-
-
 def _require_device(name, dtype, **tensors):
     for key, x in tensors.items():
         if not x.is_cuda:
             raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
         if x.dtype != dtype:
             raise RuntimeError('%s: %s must be %s, got %s' % (name, key, dtype, x.dtype))
+
+
+def _lm_args(lm, device, space_id, alpha, beta):
+    """The LM arguments of a beam search entry, ngram_table .. oov_logp in the ABI's order, and the device tables they
+    point into: keep those referenced until the call has been made.  ``alpha is None`` gives the ``_rows`` form, which has
+    no scalar weights."""
+    if lm is None:
+        tabs, args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
+    else:
+        tabs = lm.to(device)
+        word = tabs.get('word')
+        weights = (0.0, 0.0) if alpha is None else (float(alpha), float(beta))
+        args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
+                1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id) + weights + (
+                    float(lm.oov_logp),)
+    return tabs, (args[:10] + args[12:] if alpha is None else args)
+
+
+def _bias_args(name, bias_trans, bias_final, a):
+    """The context-graph arguments bias_trans, bias_final, bias_states of ``_bias`` and ``_nbest``, the shape checked."""
+    _require_device(name, torch.int32, bias_trans=bias_trans, bias_final=bias_final)
+    states = int(bias_final.numel())
+    if bias_trans.dim() != 2 or tuple(bias_trans.shape) != (states, a):
+        raise RuntimeError('%s: bias_trans must be (states, A) = (%d, %d), got %s'
+                           % (name, states, a, tuple(bias_trans.shape)))
+    return bias_trans, bias_final, states
+
+
+def _beam_search(entry, rows, ws_rows, probs, head, beam_width, blank, log_input, lm, space_id, alpha, beta, mid=(),
+                 tail=()):
+    """The call all four beam search wrappers make: the workspace for ``ws_rows`` rows, the five outputs with ``rows``
+    (a tuple) in front of their own shape, and ``entry(probs, *head, T, A, blank, beam_width, log_input, <LM>, *mid,
+    <workspace>, <outputs>, *tail)``.  Returns the five outputs."""
+    _, t, a = probs.shape
+    ws = _bytes_ws(lib.query('ds2_ctc_beam_ws_bytes', ws_rows, t, beam_width), probs)
+    labels = torch.empty(rows + (t,), dtype=torch.int32, device=probs.device)
+    offsets = torch.empty(rows + (t,), dtype=torch.int32, device=probs.device)
+    lens = torch.empty(rows, dtype=torch.int32, device=probs.device)
+    score = _empty(rows, probs)
+    ctc = _empty(rows, probs)
+    tabs, lm_args = _lm_args(lm, probs.device, space_id, alpha, beta)       # tabs: referenced until the call is made
+    lib.call(entry, probs, *head, t, a, int(blank), int(beam_width), int(bool(log_input)), *lm_args, *mid, ws,
+             ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc, *tail)
+    return labels, offsets, lens, score, ctc
+
+
+def ctc_beam_search(probs, sizes, beam_width, blank=0, log_input=False, lm=None, alpha=0.0, beta=0.0, space_id=-1):
+    """Batched CTC prefix beam search on the current stream (``ds2_ctc_beam_search_batch``).  probs (B,T,A) fp32 on the
+    device, sizes (B,) int32 on the device; ``lm`` an ``codes.lm.NGramLM`` or None.  Returns the device tensors
+    labels (B,T), offsets (B,T), lens (B,) int32 and score, ctc_logp (B,) fp32."""
+    bsz = probs.shape[0]
+    return _beam_search('ds2_ctc_beam_search_batch', (bsz,), bsz, probs, (sizes, bsz), beam_width, blank, log_input, lm,
+                        space_id, alpha, beta)
 
 
 def ctc_beam_search_rows(probs, sizes, utt, alpha, beta, beam_width, blank=0, log_input=False, lm=None, space_id=-1):
@@ -1075,27 +1103,12 @@ def ctc_beam_search_rows(probs, sizes, utt, alpha, beta, beam_width, blank=0, lo
     the empty labelling at -inf.  Nothing waits on the stream."""
     _require_device('ctc_beam_search_rows', torch.float32, probs=probs, alpha=alpha, beta=beta)
     _require_device('ctc_beam_search_rows', torch.int32, sizes=sizes, utt=utt)
-    bsz, t, a = probs.shape
+    bsz = probs.shape[0]
     rows = int(utt.numel())
     if int(sizes.numel()) != bsz or int(alpha.numel()) != rows or int(beta.numel()) != rows:
         raise RuntimeError('ctc_beam_search_rows: sizes must have B entries; alpha and beta one per entry of utt')
-    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', rows, t, beam_width)
-    ws = _bytes_ws(ws_bytes, probs)
-    labels = torch.empty((rows, t), dtype=torch.int32, device=probs.device)
-    offsets = torch.empty((rows, t), dtype=torch.int32, device=probs.device)
-    lens = torch.empty((rows,), dtype=torch.int32, device=probs.device)
-    score = _empty((rows,), probs)
-    ctc = _empty((rows,), probs)
-    if lm is None:
-        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0)
-    else:
-        tabs = lm.to(probs.device)
-        word = tabs.get('word')
-        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
-                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(lm.oov_logp))
-    lib.call('ds2_ctc_beam_search_rows', probs, sizes, utt, alpha, beta, bsz, rows, t, a, int(blank), int(beam_width),
-             int(bool(log_input)), *lm_args, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc)
-    return labels, offsets, lens, score, ctc
+    return _beam_search('ds2_ctc_beam_search_rows', (rows,), rows, probs, (sizes, utt, alpha, beta, bsz, rows), beam_width,
+                        blank, log_input, lm, space_id, None, None)
 
 
 def ctc_beam_search_bias(probs, sizes, beam_width, bias_trans, bias_final, bias_weight, blank=0, log_input=False, lm=None,
@@ -1105,32 +1118,12 @@ def ctc_beam_search_bias(probs, sizes, beam_width, bias_trans, bias_final, bias_
     bias_weight the weight per matched label in nats.  Returns ``ctc_beam_search``'s five device tensors and bias (B,)
     int32: the labels of each returned labelling that the boosted phrases cover.  Nothing waits on the stream."""
     _require_device('ctc_beam_search_bias', torch.float32, probs=probs)
-    _require_device('ctc_beam_search_bias', torch.int32, sizes=sizes, bias_trans=bias_trans, bias_final=bias_final)
-    bsz, t, a = probs.shape
-    states = int(bias_final.numel())
-    if bias_trans.dim() != 2 or tuple(bias_trans.shape) != (states, a):
-        raise RuntimeError('ctc_beam_search_bias: bias_trans must be (states, A) = (%d, %d), got %s'
-                           % (states, a, tuple(bias_trans.shape)))
-    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
-    ws = _bytes_ws(ws_bytes, probs)
-    labels = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    offsets = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    lens = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
-    score = _empty((bsz,), probs)
-    ctc = _empty((bsz,), probs)
+    _require_device('ctc_beam_search_bias', torch.int32, sizes=sizes)
+    bsz, _, a = probs.shape
+    graph = _bias_args('ctc_beam_search_bias', bias_trans, bias_final, a) + (float(bias_weight),)
     bias = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
-    if lm is None:
-        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
-    else:
-        tabs = lm.to(probs.device)
-        word = tabs.get('word')
-        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
-                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
-                   float(beta), float(lm.oov_logp))
-    lib.call('ds2_ctc_beam_search_bias', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
-             *lm_args, bias_trans, bias_final, states, float(bias_weight), ws, ws.numel() * ws.element_size(), labels,
-             offsets, lens, score, ctc, bias)
-    return labels, offsets, lens, score, ctc, bias
+    return _beam_search('ds2_ctc_beam_search_bias', (bsz,), bsz, probs, (sizes, bsz), beam_width, blank, log_input, lm,
+                        space_id, alpha, beta, mid=graph, tail=(bias,)) + (bias,)
 
 
 def ctc_beam_search_nbest(probs, sizes, beam_width, nbest, blank=0, log_input=False, lm=None, alpha=0.0, beta=0.0,
@@ -1143,40 +1136,19 @@ def ctc_beam_search_nbest(probs, sizes, beam_width, nbest, blank=0, log_input=Fa
     empty at -inf.  Nothing waits on the stream."""
     _require_device('ctc_beam_search_nbest', torch.float32, probs=probs)
     _require_device('ctc_beam_search_nbest', torch.int32, sizes=sizes)
-    bsz, t, a = probs.shape
+    bsz, _, a = probs.shape
     n = int(nbest)
     if not 1 <= n <= int(beam_width):
         raise ValueError('ctc_beam_search_nbest: nbest %d is outside 1..beam_width = %d' % (n, int(beam_width)))
-    bias, bias_args = None, (None, None, 0, 0.0)
+    bias, graph = None, (None, None, 0, 0.0)
     if bias_trans is not None:
         if bias_final is None:
             raise RuntimeError('ctc_beam_search_nbest: bias_trans needs bias_final')
-        _require_device('ctc_beam_search_nbest', torch.int32, bias_trans=bias_trans, bias_final=bias_final)
-        states = int(bias_final.numel())
-        if bias_trans.dim() != 2 or tuple(bias_trans.shape) != (states, a):
-            raise RuntimeError('ctc_beam_search_nbest: bias_trans must be (states, A) = (%d, %d), got %s'
-                               % (states, a, tuple(bias_trans.shape)))
+        graph = _bias_args('ctc_beam_search_nbest', bias_trans, bias_final, a) + (float(bias_weight),)
         bias = torch.empty((bsz, n), dtype=torch.int32, device=probs.device)
-        bias_args = (bias_trans, bias_final, states, float(bias_weight))
-    ws_bytes = lib.query('ds2_ctc_beam_ws_bytes', bsz, t, beam_width)
-    ws = _bytes_ws(ws_bytes, probs)
-    labels = torch.empty((bsz, n, t), dtype=torch.int32, device=probs.device)
-    offsets = torch.empty((bsz, n, t), dtype=torch.int32, device=probs.device)
-    lens = torch.empty((bsz, n), dtype=torch.int32, device=probs.device)
-    score = _empty((bsz, n), probs)
-    ctc = _empty((bsz, n), probs)
     count = torch.empty((bsz,), dtype=torch.int32, device=probs.device)
-    if lm is None:
-        tabs, lm_args = {}, (None, 0, None, 0, 1, 0, -1, -1, -1, -1, 0.0, 0.0, 0.0)
-    else:
-        tabs = lm.to(probs.device)
-        word = tabs.get('word')
-        lm_args = (tabs['ngram'], tabs['ngram'].shape[0], word, 0 if word is None else word.shape[0], lm.order,
-                   1 if lm.unit == 'char' else 2, lm.bos_id, lm.eos_id, lm.hist_unk_id, space_id, float(alpha),
-                   float(beta), float(lm.oov_logp))
-    lib.call('ds2_ctc_beam_search_nbest', probs, sizes, bsz, t, a, int(blank), int(beam_width), int(bool(log_input)),
-             *lm_args, *bias_args, n, ws, ws.numel() * ws.element_size(), labels, offsets, lens, score, ctc, bias, count)
-    return labels, offsets, lens, score, ctc, bias, count
+    return _beam_search('ds2_ctc_beam_search_nbest', (bsz, n), bsz, probs, (sizes, bsz), beam_width, blank, log_input, lm,
+                        space_id, alpha, beta, mid=graph + (n,), tail=(bias, count)) + (bias, count)
 
 
 EDIT_MAX_ITEMS = lib.EDIT_MAX_ITEMS     # DS2_EDIT_MAX_ITEMS of include/ds2hip.h: labels per side ds2_edit_stats takes

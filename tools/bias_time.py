@@ -11,11 +11,7 @@ labels cut from the generated text (so that they do occur).  Device events, medi
 import argparse
 import json
 import os
-import subprocess
 import sys
-import tempfile
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
@@ -30,33 +26,14 @@ def main():
     ap.add_argument('--out', default=None, help='directory for the generated LM (default: a temporary one)')
     args = ap.parse_args()
     import torch
-    from beam_time import LABELS, WORDS
+    from beam_time import B, LABELS, T, seeded_input, timed
     from codes.bias import PhraseBooster
-    from codes.lm import NGramLM
     from ds2hip import ops
     assert torch.cuda.is_available(), 'bias_time.py measures on the GPU'
-    rng = np.random.default_rng(0)
-    out = args.out or tempfile.mkdtemp()
-    os.makedirs(out, exist_ok=True)
-    text = os.path.join(out, 'text.txt')
-    sents = [' '.join(rng.choice(WORDS, size=rng.integers(4, 20))) for _ in range(2000)]
-    with open(text, 'w') as f:
-        f.write('\n'.join(sents) + '\n')
-    path = os.path.join(out, 'word3.arpa')
-    subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'make_lm.py'), '--order', '3', '--unit', 'word',
-                    '--text', text, '-o', path], check=True, capture_output=True)
-    lms = {'none': None, 'word3': NGramLM.from_arpa(path, LABELS, unit='word')}
-    B, T, A = 32, 746, len(LABELS)
-    x = rng.standard_normal((B, T, A)) * 1.5
-    spoken = []
-    for b in range(B):                       # frames spelling a sentence: letter, then blank
-        s = ' '.join(sents[1000 + b * 3:1000 + b * 3 + 6])[:T // 2]
-        spoken.append(s)
-        for i, ch in enumerate(s):
-            x[b, 2 * i, LABELS.index(ch)] += 4.0
-            x[b, 2 * i + 1, 0] += 3.0
-    e = np.exp(x - x.max(-1, keepdims=True))
-    probs = torch.from_numpy((e / e.sum(-1, keepdims=True)).astype(np.float32)).cuda()
+    probs, spoken, sents, lms = seeded_input(args.out, ('word3',))
+    probs = torch.from_numpy(probs).cuda()
+    lms = {'none': None, 'word3': lms['word3']}
+    A = len(LABELS)
     sizes = torch.full((B,), T, dtype=torch.int32, device='cuda')
     phrases, k = [], 0
     while len(phrases) < 100:                # 8-label cuts of what is spoken, then of the rest of the text
@@ -69,26 +46,12 @@ def main():
     trans, final = booster.tables(probs.device)
     res = {'B': B, 'T': T, 'A': A, 'phrases': len(phrases), 'phrase_labels': 8, 'states': booster.graph.n_states,
            'weight': args.weight, 'batch_ms': {}, 'bias_ms': {}, 'ratio': {}, 'boosted_labels': {}}
-
-    def timed(run):
-        run()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            run()
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return float(np.median(ts))
-
     for w in [int(v) for v in args.widths.split(',')]:
         for name, lm in lms.items():
             key = 'W%d_%s' % (w, name)
-            plain = timed(lambda: ops.ctc_beam_search(probs, sizes, w, 0, False, lm, 0.5, 1.0, 1))
+            plain = timed(lambda: ops.ctc_beam_search(probs, sizes, w, 0, False, lm, 0.5, 1.0, 1), args.reps)[0]
             bias = timed(lambda: ops.ctc_beam_search_bias(probs, sizes, w, trans, final, args.weight, 0, False, lm, 0.5,
-                                                          1.0, 1))
+                                                          1.0, 1), args.reps)[0]
             res['batch_ms'][key], res['bias_ms'][key] = round(plain, 3), round(bias, 3)
             res['ratio'][key] = round(bias / plain, 3)
             res['boosted_labels'][key] = int(ops.ctc_beam_search_bias(probs, sizes, w, trans, final, args.weight, 0, False,

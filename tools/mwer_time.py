@@ -30,6 +30,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     args = ap.parse_args()
     import torch
+    import beam_time
     from beam_time import LABELS, WORDS
     from codes.ctc import ctc_costs_and_grad, mwer_costs_and_grad
     from ds2hip import ops
@@ -51,17 +52,7 @@ def main():
     act_lens = torch.full((B,), T, dtype=torch.int32)
 
     def timed(run):
-        run()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            run()
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return round(float(np.median(ts)), 3), round(float(max(ts) - min(ts)), 3)
+        return tuple(round(v, 3) for v in beam_time.timed(run, args.reps)[:2])
 
     res = {'B': B, 'T': T, 'A': A, 'N': N, 'W': W, 'mean_ref_len': round(float(sizes.float().mean()), 1)}
     _, _, info = mwer_costs_and_grad(acts, targets, act_lens, sizes, space, nbest=N, beam_width=W)

@@ -15,16 +15,14 @@ Needs no corpus.  The numbers in DESIGN.md "LM weight tuning" are this tool's.
 import argparse
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'aes-lac-2018_amd'))
 sys.path.insert(0, ROOT)
-from tools.beam_time import LABELS, WORDS  # noqa: E402
+from tools.beam_time import B, LABELS, T, seeded_input, timed  # noqa: E402
 
 
 def main():
@@ -38,53 +36,16 @@ def main():
     import torch
     from codes import tune
     from codes.decoder import DeviceBeamCTCDecoder
-    from codes.lm import NGramLM
     from ds2hip import ops
     assert torch.cuda.is_available(), 'tune_time.py measures on the GPU'
-    rng = np.random.default_rng(0)
-    out = args.out or tempfile.mkdtemp()
-    os.makedirs(out, exist_ok=True)
-    text = os.path.join(out, 'text.txt')
-    sents = [' '.join(rng.choice(WORDS, size=rng.integers(4, 20))) for _ in range(2000)]
-    with open(text, 'w') as f:
-        f.write('\n'.join(sents) + '\n')
-    lms = {}
-    for name, order, unit in (('char6', 6, 'char'), ('word3', 3, 'word')):
-        if name not in args.lms.split(','):
-            continue
-        path = os.path.join(out, name + '.arpa')
-        subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'make_lm.py'), '--order', str(order), '--unit', unit,
-                        '--text', text, '-o', path], check=True, capture_output=True)
-        lms[name] = NGramLM.from_arpa(path, LABELS, unit=unit)
-    B, T, A = 32, 746, len(LABELS)
-    x = rng.standard_normal((B, T, A)) * 1.5
-    refs = []
-    for b in range(B):                       # frames spelling a sentence: letter, then blank
-        s = ' '.join(sents[1000 + b * 3:1000 + b * 3 + 6])[:T // 2]
-        refs.append(s)
-        for i, ch in enumerate(s):
-            x[b, 2 * i, LABELS.index(ch)] += 4.0
-            x[b, 2 * i + 1, 0] += 3.0
-    e = np.exp(x - x.max(-1, keepdims=True))
-    probs = torch.from_numpy((e / e.sum(-1, keepdims=True)).astype(np.float32)).cuda()
+    probs, refs, _, lms = seeded_input(args.out, args.lms.split(','))
+    probs = torch.from_numpy(probs).cuda()
+    A = len(LABELS)
     sizes = torch.full((B,), T, dtype=torch.int32, device='cuda')
     targets = torch.tensor([LABELS.index(c) for r in refs for c in r], dtype=torch.int32, device='cuda')
     target_sizes = torch.tensor([len(r) for r in refs], dtype=torch.int32)
     alphas = [round(0.25 * k, 2) for k in range(8)]
     betas = [round(0.5 * k, 2) for k in range(8)]
-
-    def timed(fn, reps):
-        fn()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            val = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return round(float(np.median(ts)), 2), val
 
     res = {'B': B, 'T': T, 'A': A, 'grid_points': len(alphas) * len(betas), 'reps': args.reps, 'per_point_ms': {},
            'tuner_ms': {}, 'beam_ms': {}, 'edit_ms': {}, 'launches': {}, 'agree': True}
@@ -102,7 +63,8 @@ def main():
                                       sum(dec.cer(h[0], r) for h, r in zip(decoded, refs))))
                 return table
 
-            res['per_point_ms'][key], want = timed(per_point, args.reps)
+            ms, _, want = timed(per_point, args.reps)
+            res['per_point_ms'][key] = round(ms, 2)
             for rows in [int(v) for v in args.rows.split(',')]:
                 def sweep():
                     t = tune.LMTuner(LABELS, lm, w, alphas, betas, rows_per_launch=rows)
@@ -110,7 +72,8 @@ def main():
                     return t.result(), t.launches
 
                 rkey = '%s_rows%d' % (key, rows)
-                res['tuner_ms'][rkey], (table, launches) = timed(sweep, args.reps)
+                ms, _, (table, launches) = timed(sweep, args.reps)
+                res['tuner_ms'][rkey] = round(ms, 2)
                 res['launches'][rkey] = launches
                 res['agree'] = res['agree'] and [(g['word_dist'], g['char_dist']) for g in table['grid']] == want
                 # the two launches on their own: the same sweep with an event pair around every call
