@@ -521,11 +521,9 @@ def test_gru_recurrence_fwd_bwd(ops, monkeypatch, mode, t, bsz, n_in, hid):
         np.testing.assert_allclose(dw_hh_r.cpu().numpy(), gru.weight_hh_l0_reverse.grad.numpy(), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize('fwd_form,bwd_form', [('4', '4'), ('16', '16'), ('4', '16'), ('16', '4')])
-@pytest.mark.parametrize('t,bsz,hid', [(7, 10, 800), (5, 27, 256), (4, 32, 800), (6, 5, 64), (9, 8, 800)])
-def test_gru_persistent_mfma_forms_agree_with_step_kernels(ops, monkeypatch, fwd_form, bwd_form, t, bsz, hid):
-    """Both MFMA forms of each persistent kernel (4x4x1 and 16x16x4; the default depends on the batch size) against
-    the launch-per-step kernels on the same inputs."""
+def _persistent_forms_against_step_kernels(ops, monkeypatch, t, bsz, hid, env):
+    """One forward and one backward recurrence with the persistent kernels that ``env`` selects, against the launch-per-step
+    kernels on the same inputs."""
     torch.manual_seed(t + bsz)
     k = 1.0 / hid ** 0.5
     w_hh = ((torch.rand(2, 3 * hid, hid) * 2 - 1) * k).to(DEV)
@@ -535,8 +533,8 @@ def test_gru_persistent_mfma_forms_agree_with_step_kernels(ops, monkeypatch, fwd
     res = {}
     for mode in ('step', 'persistent'):
         monkeypatch.setattr(ops, 'GRU_MODE', mode)
-        monkeypatch.setenv('DS2_GRU_FWD', fwd_form)
-        monkeypatch.setenv('DS2_GRU_BWD', bwd_form)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
         g = gi.clone()
         ghn, hout = ops.gru_bidir_fwd(g, w_hh, t, bsz, hid)
         fwd = (g.clone(), ghn.clone(), hout.clone())
@@ -546,6 +544,33 @@ def test_gru_persistent_mfma_forms_agree_with_step_kernels(ops, monkeypatch, fwd
         res[mode] = fwd + (g, ghn)
     for a, b in zip(res['persistent'], res['step']):
         np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=3e-5, rtol=1e-4)
+
+
+@pytest.mark.parametrize('fwd_form,bwd_form', [('4', '4'), ('16', '16'), ('4', '16'), ('16', '4')])
+@pytest.mark.parametrize('t,bsz,hid', [(7, 10, 800), (5, 27, 256), (4, 32, 800), (6, 5, 64), (9, 8, 800)])
+def test_gru_persistent_mfma_forms_agree_with_step_kernels(ops, monkeypatch, fwd_form, bwd_form, t, bsz, hid):
+    """Both MFMA forms of each persistent kernel (4x4x1 and 16x16x4; the default depends on the batch size) against
+    the launch-per-step kernels on the same inputs."""
+    _persistent_forms_against_step_kernels(ops, monkeypatch, t, bsz, hid, {'DS2_GRU_FWD': fwd_form, 'DS2_GRU_BWD': bwd_form})
+
+
+_P16_FP32 = {'DS2_GRU_P2_BF16': '0', 'DS2_GRU_P2_BF16_BWD': '0'}
+_P16_BF16 = {'DS2_GRU_P2_BF16': '1', 'DS2_GRU_P2_BF16_BWD': '1'}
+
+
+@pytest.mark.parametrize('bsz,env', [(5, {'DS2_GRU_FWD': '16', 'DS2_GRU_BWD': '16'}), (17, _P16_FP32), (17, _P16_BF16),
+                                     (33, _P16_FP32), (33, _P16_BF16)],
+                         ids=['b5-whole', 'b17-fp32', 'b17-bf16', 'b33-fp32', 'b33-bf16'])
+@pytest.mark.parametrize('hid', [32, 64, 128, 256, 384])
+def test_gru_persistent_16x16_narrow_widths_agree_with_step_kernels(ops, monkeypatch, hid, bsz, env):
+    """The instantiations of the 16x16 kernels (gru_persist16.hip) that the H = 800 cases do not reach: these five widths run
+    k blocks per wave (KBW) 1, 1, 1, 2, 4 (forward fp32), 1, 1, 1, 1, 2 (forward bf16), 1, 2, 4, 8, 19 (backward fp32) and
+    1, 1, 2, 5, 5 (backward bf16).  B = 5: the whole-batch forms with 5 live rows of one tile; B = 17: the two-part forms
+    with parts of 9 and 8 rows; B = 33: two batch tiles per part, 17 rows (one in the second tile) and 16 (an empty second
+    tile).  T = 5 uses both ring slots and a steady-state step.  The whole-batch forms with 2 and 4 batch tiles exist in the
+    tuning library only and are not run here."""
+    _persistent_forms_against_step_kernels(ops, monkeypatch, 5, bsz, hid, dict(env, DS2_GRU_BWD_DH='0'))
+    assert not ops._persistent_off
 
 
 def _long_sequence_case(ops, monkeypatch, bsz, reps, during=None, spare_cus=(-1,)):

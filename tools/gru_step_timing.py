@@ -20,4 +20,6 @@ for _ in range(6):
     ops.gru_bidir_bwd(g, ghn, hout, d_out, w_hh_t, t, bsz, hid, spare_cus=spare, coef=coef); e[2].record(); torch.cuda.synchronize()
     res['fwd'].append(e[0].elapsed_time(e[1])*1e3/t); res['bwd'].append(e[1].elapsed_time(e[2])*1e3/t)
 print('T=%d ' % t, end='')
-print('DBG=%s B=%d spare_cus=%d  fwd %.2f us/step  bwd %.2f us/step' % (os.environ.get('DS2_GRU_DBG','0'), bsz, spare, np.median(res['fwd']), np.median(res['bwd'])))
+spread = {k: max(v) - min(v) for k, v in res.items()}    # max - min of the six launches
+print('DBG=%s B=%d spare_cus=%d  fwd %.3f us/step (spread %.3f)  bwd %.3f us/step (spread %.3f)' % (
+    os.environ.get('DS2_GRU_DBG','0'), bsz, spare, np.median(res['fwd']), spread['fwd'], np.median(res['bwd']), spread['bwd']))
