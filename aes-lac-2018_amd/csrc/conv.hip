@@ -651,6 +651,7 @@ extern "C" int ds2_conv_fwd(int which, const float* in, const float* weight, con
     DS2_CHECK_ARG(which == 1 || which == 2);
     DS2_CHECK_ARG(in && weight && bias && out && wt_ws && B > 0);
     const ConvGeom g = geom(which);
+    DS2_CHECK_ARG(t_in_frames > 0);   // (conv1: C division truncates, so conv_tout alone lets -10 .. 0 frames through)
     const int tin = t_in_frames, tout = conv_tout(which, tin);
     DS2_CHECK_ARG(tout > 0);
     hipStream_t st = (hipStream_t)stream;
@@ -754,6 +755,7 @@ extern "C" int ds2_conv_wgrad(int which, const float* in, const float* d_out, in
     DS2_CHECK_ARG(which == 1 || which == 2);
     DS2_CHECK_ARG(in && d_out && d_weight && d_bias && B > 0);
     const ConvGeom g = geom(which);
+    DS2_CHECK_ARG(t_in_frames > 0);   // (conv1: C division truncates, so conv_tout alone lets -10 .. 0 frames through)
     const int tin = t_in_frames, tout = conv_tout(which, tin);
     DS2_CHECK_ARG(tout > 0);
     hipStream_t st = (hipStream_t)stream;
