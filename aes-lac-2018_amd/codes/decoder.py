@@ -15,6 +15,7 @@ import torch
 
 from ds2hip import lib, ops
 
+from .confidence import UnitConfidence, check_decoder_confidence, nbest_rows
 from .preprocessing import OrderedLabelEncoder
 
 
@@ -77,6 +78,15 @@ class Decoder(object):
 
 
 class GreedyDecoder(Decoder):
+    """``confidence``: a ``codes.confidence.UnitConfidence`` made for the same alphabet and blank; ``decode`` then scores
+    the label rows it holds on the device against the probabilities it was given and sets ``last_confidences[b][n]``, the
+    list of values (one per word, or per character) of ``strings[b][n]``.  Without one nothing changes."""
+
+    def __init__(self, label_encoder, blank_index=0, confidence=None):
+        super().__init__(label_encoder, blank_index)
+        self.confidence = check_decoder_confidence(self, confidence)
+        self.last_confidences = None
+
     def _to_string(self, ids):
         if len(ids) == 0:
             return ''
@@ -110,6 +120,9 @@ class GreedyDecoder(Decoder):
         best = ops.argmax_rows(flat, bsz * t, a).view(bsz, t)
         sizes_d = _device_sizes(probs, sizes)
         ids, offs, lens = ops.greedy_collapse(best, sizes_d, self.blank_index)
+        if self.confidence is not None:
+            scored = self.confidence.score(probs, sizes_d, ids, offs, lens)
+            self.last_confidences = [[c] for c in UnitConfidence.lists_from(scored)]
         ids, offs, lens = ids.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
         strings = [[self._to_string(ids[b, :lens[b]])] for b in range(bsz)]
         offsets = [[torch.IntTensor(offs[b, :lens[b]].copy())] for b in range(bsz)]
@@ -183,11 +196,15 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     the returned float32 fused scores, in float64 (``nbest_posteriors``): a weight AMONG THE RETURNED ALTERNATIVES UNDER
     THE FUSED SCORE, not a calibrated probability -- the score holds alpha, beta and the boost, the list ends at
     ``nbest``, and nobody has measured its calibration on a trained model.  With ``nbest == 1`` nothing changes: the
-    1-best entries are called with the arguments they get today and the ``last_nbest_*`` fields stay None."""
+    1-best entries are called with the arguments they get today and the ``last_nbest_*`` fields stay None.
+
+    ``confidence``: as for ``GreedyDecoder``; ``last_confidences[b][n]`` covers every returned alternative (the rows of an
+    N-best result are scored in one call, each against its own utterance).  The values are acoustic: no LM, no boost."""
 
     def __init__(self, label_encoder, blank_index=0, beam_width=16, lm=None, alpha=0.0, beta=0.0, log_input=False,
-                 booster=None, nbest=1):
-        super().__init__(label_encoder, blank_index)
+                 booster=None, nbest=1, confidence=None):
+        self.log_input = bool(log_input)                       # (before the check of ``confidence``, which refuses it)
+        super().__init__(label_encoder, blank_index, confidence)
         if not 1 <= beam_width <= 128:
             raise ValueError('beam_width must be in 1..128 for the device search, got %d' % beam_width)
         if not 1 <= nbest <= beam_width:
@@ -246,6 +263,9 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
     def _decode_nbest(self, probs, sizes_d):
         bsz = probs.shape[0]
         labels, offs, lens, score, ctc, bias, count = self._search_nbest(probs, sizes_d)
+        conf = None
+        if self.confidence is not None:
+            conf = UnitConfidence.lists_from(self.confidence.score(probs, sizes_d, *nbest_rows(labels, offs, lens)))
         labels, offs, lens, count = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy(), count.cpu().numpy()
         score, ctc = score.cpu().numpy(), ctc.cpu().numpy()
         keep = [max(1, int(c)) for c in count]
@@ -258,6 +278,8 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
             bias = bias.cpu().numpy()
             self.last_bias_counts = bias[:, 0].tolist()
             self.last_nbest_bias_counts = [bias[b, :keep[b]].tolist() for b in range(bsz)]
+        if conf is not None:
+            self.last_confidences = [[conf[b * self.nbest + n] for n in range(keep[b])] for b in range(bsz)]
         strings = [[self._to_string(labels[b, n, :lens[b, n]]) for n in range(keep[b])] for b in range(bsz)]
         offsets = [[torch.IntTensor(offs[b, n, :lens[b, n]].copy()) for n in range(keep[b])] for b in range(bsz)]
         return strings, offsets
@@ -270,6 +292,9 @@ class DeviceBeamCTCDecoder(GreedyDecoder):
             return self._decode_nbest(probs, sizes_d)
         bsz = probs.shape[0]
         labels, offs, lens, score, ctc, bias = self._search(probs, sizes_d)
+        if self.confidence is not None:
+            scored = self.confidence.score(probs, sizes_d, labels, offs, lens)
+            self.last_confidences = [[c] for c in UnitConfidence.lists_from(scored)]
         labels, offs, lens = labels.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
         if bias is not None:
             self.last_bias_counts = bias.cpu().tolist()

@@ -21,6 +21,34 @@ def rates(total):
     return out
 
 
+def word_matches(hyp_words, ref_words):
+    """Which hypothesis words does a minimal word alignment keep: ``[bool]`` as long as ``hyp_words``.  The Levenshtein
+    table over words is back-traced from its end; at each cell the diagonal is taken if it keeps the distance, then the step
+    that drops a hypothesis word, then the step that drops a reference word.  A hypothesis word is correct if and only if
+    it lies on a diagonal step with equal words."""
+    hyp, ref = list(hyp_words), list(ref_words)
+    m, n = len(hyp), len(ref)
+    d = [[0] * (n + 1) for _ in range(m + 1)]
+    for i in range(m + 1):
+        d[i][0] = i
+    for j in range(n + 1):
+        d[0][j] = j
+    for i in range(1, m + 1):
+        for j in range(1, n + 1):
+            d[i][j] = min(d[i - 1][j - 1] + (hyp[i - 1] != ref[j - 1]), d[i - 1][j] + 1, d[i][j - 1] + 1)
+    correct = [False] * m
+    i, j = m, n
+    while i > 0 or j > 0:
+        if i > 0 and j > 0 and d[i][j] == d[i - 1][j - 1] + (hyp[i - 1] != ref[j - 1]):
+            correct[i - 1] = hyp[i - 1] == ref[j - 1]
+            i, j = i - 1, j - 1
+        elif i > 0 and d[i][j] == d[i - 1][j] + 1:
+            i -= 1
+        else:
+            j -= 1
+    return correct
+
+
 def target_layout(targets, target_sizes, device):
     """The loader's flat ``targets`` and ``target_sizes`` as the device tensors ``ops.edit_stats`` takes:
     (ref, ref_offsets, ref_lens, max_ref_len).  The one host step is the maximum over the HOST sizes."""

@@ -108,6 +108,8 @@ SIGNATURES = {
     'ds2_ctc_align_banded': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     'ds2_ctc_keyword_search_ws_bytes': (_Z, [_I, _I]),
     'ds2_ctc_keyword_search': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P]),
+    'ds2_ctc_unit_posterior_ws_bytes': (_Z, [_I, _I, _I]),
+    'ds2_ctc_unit_posterior': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 404            # DS2_ABI_VERSION of include/ds2hip.h: the revision this table (and ops.py) is written against
@@ -117,6 +119,7 @@ _lib = None
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3           # DS2_ERR_* of include/ds2hip.h
 ALIGN_BAND_MIN, ALIGN_BAND_MAX = 64, 8192                   # DS2_ALIGN_BAND_* of include/ds2hip.h (ds2_ctc_align_banded)
 KWS_MAX_LEN = 64                                            # DS2_KWS_MAX_LEN of include/ds2hip.h (ds2_ctc_keyword_search)
+UNIT_MAX_LABELS = 64                                        # DS2_UNIT_MAX_LABELS of include/ds2hip.h (ds2_ctc_unit_posterior)
 BIAS_MAX_LEN, BIAS_MAX_PHRASES, BIAS_MAX_STATES = 64, 1024, 32768   # DS2_BIAS_MAX_* of include/ds2hip.h (phrase boosting)
 MWER_MAX_NBEST = 128                                       # DS2_MWER_MAX_NBEST of include/ds2hip.h (ds2_ctc_mwer_grad)
 EDIT_MAX_ITEMS = 2048                                      # DS2_EDIT_MAX_ITEMS of include/ds2hip.h (ds2_edit_stats)

@@ -1274,6 +1274,50 @@ def keyword_search(logp, sizes, labels, label_offsets, label_lens, min_score, ma
     return hits, hit_score, n_hits
 
 
+UNIT_MAX_LABELS = lib.UNIT_MAX_LABELS   # DS2_UNIT_MAX_LABELS of include/ds2hip.h: labels of a unit ds2_ctc_unit_posterior scores
+
+
+def ctc_unit_posterior(probs, sizes, labels, offsets, lens, utt=None, space_id=-1, blank=0, max_units=None, ws=None):
+    """The span posterior of every word (``space_id >= 0``) or character (``space_id = -1``) of R decoded label rows, in one
+    call on the current stream (``ds2_ctc_unit_posterior``; include/ds2hip.h, "unit posterior", has the definition).  probs
+    (B,T,A) fp32 PROBABILITIES and sizes (B,) int32 on the device; labels, offsets (R,stride) and lens (R,) int32 on the device
+    as the beam search and ``greedy_collapse`` return them (an N-best result viewed as (B*N, T)); ``utt`` (R,) int32 is each
+    row's utterance (None: row r uses utterance r).  ``max_units`` defaults to stride (characters) or (stride + 1) // 2
+    (words), which no row can exceed.  ``ws``: a uint8 device tensor of at least ``ds2_ctc_unit_posterior_ws_bytes(R, stride,
+    max_units)`` bytes, or None to allocate one.  Returns the device tensors unit_first, unit_len (R,max_units) int32 (-1 past
+    the count), unit_logp (R,max_units) float64 (NaN past the count and for a unit of more than ``UNIT_MAX_LABELS`` labels),
+    n_units (R,) int32 (the true count; -1 for an invalid row) and dropped (R,) int32.  Nothing waits on the stream."""
+    _require_device('ctc_unit_posterior', torch.float32, probs=probs)
+    ints = dict(sizes=sizes, labels=labels, offsets=offsets, lens=lens)
+    if utt is not None:
+        ints['utt'] = utt
+    _require_device('ctc_unit_posterior', torch.int32, **ints)
+    if probs.dim() != 3 or labels.dim() != 2 or tuple(offsets.shape) != tuple(labels.shape):
+        raise RuntimeError('ctc_unit_posterior: probs must be (B,T,A); labels and offsets (R,stride)')
+    bsz, t, a = probs.shape
+    rows, stride = labels.shape
+    if int(sizes.numel()) != bsz or int(lens.numel()) != rows or (utt is not None and int(utt.numel()) != rows):
+        raise RuntimeError('ctc_unit_posterior: sizes must have B entries; lens and utt R entries')
+    if utt is None and rows > bsz:
+        raise RuntimeError('ctc_unit_posterior: %d rows of %d utterances need utt' % (rows, bsz))
+    space_id = int(space_id)
+    if max_units is None:
+        max_units = stride if space_id < 0 else (stride + 1) // 2
+    max_units = int(max_units)
+    if ws is None:
+        ws_bytes = lib.query('ds2_ctc_unit_posterior_ws_bytes', rows, stride, max_units)
+        ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
+    shape = (max(rows, 0), max(max_units, 0))
+    unit_first = torch.empty(shape, dtype=torch.int32, device=probs.device)
+    unit_len = torch.empty(shape, dtype=torch.int32, device=probs.device)
+    unit_logp = torch.empty(shape, dtype=torch.float64, device=probs.device)
+    n_units = torch.empty(shape[:1], dtype=torch.int32, device=probs.device)
+    dropped = torch.empty(shape[:1], dtype=torch.int32, device=probs.device)
+    lib.call('ds2_ctc_unit_posterior', probs, sizes, bsz, t, a, labels, offsets, lens, utt, rows, stride, space_id, int(blank),
+             max_units, ws, ws.numel() * ws.element_size(), unit_first, unit_len, unit_logp, n_units, dropped)
+    return unit_first, unit_len, unit_logp, n_units, dropped
+
+
 # ----------------------------------------------------------------------------- CTC
 def ctc_loss_grad(acts, labels, label_offsets, label_lens, act_lens, max_label_len, grad_scale=1.0,
                   zero_batch_if_inf=False):

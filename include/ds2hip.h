@@ -741,6 +741,48 @@ int ds2_ctc_keyword_search(const float* logp, const int32_t* sizes, const int32_
                            int max_hits, void* ws, size_t ws_bytes, int32_t* hits, double* hit_score, int32_t* n_hits,
                            void* stream);
 
+/* ------------------------------------------------------------------ unit posterior (csrc/ctc_unit.hip)
+ * Not in the reference, so every rule here is this project's decision.  How sure is the model of each WORD (or character) of a
+ * decoded label row: the probability, under the model's own frame posteriors, that the frames the decoder gave the unit spell
+ * exactly that unit.  Acoustic only: no LM, no boost.  Every (row, unit) is independent of every other.
+ * probs (B,T,A): fp32 PROBABILITIES (there is no log_input switch).  sizes (B).  labels / offsets (R,stride) and lens (R): the
+ * layout ds2_greedy_collapse and the beam searches return (an N-best result viewed as (B N, T)); utt (R) is each row's
+ * utterance, NULL meaning row r belongs to utterance r.
+ *   units      space_id >= 0 (words): a unit is a maximal run of labels other than space_id -- leading, trailing and repeated
+ *              spaces make no unit.  space_id = -1 (characters): every label is its own unit.  Units are numbered in row order.
+ *   span       a unit of labels i .. j-1 (L = j - i >= 1) covers the frames o[i] .. o[j-1] INCLUSIVE of its utterance, n of
+ *              them: the offsets the decoder reported for its first and last label, so the span is tight.
+ *   value      P = the sum, over all CTC alignments pi of the span's n frames that collapse to the unit's labels, of
+ *              prod_t probs[utt][o[i] + t][pi_t]: the CTC forward over the S = 2 L + 1 states blank, l1, blank, .., lL, blank
+ *              (blanks allowed at both ends) on the sub-matrix of the span.  0 <= P <= 1 for normalised rows, and over all
+ *              labellings of the span the values sum to 1.  A frame spent on another symbol costs exactly that symbol's share.
+ *   arithmetic linear, fp64: alpha[0][0] = p[0][blank], alpha[0][1] = p[0][l1];  alpha[t][s] = p[t][ext[s]] * (alpha[t-1][s] +
+ *              alpha[t-1][s-1] (+ alpha[t-1][s-2] if s is a label state and ext[s] != ext[s-2])).  Every fp32 probability is
+ *              converted to double (exact); a NaN or negative one counts as 0.  All alphas of a unit are rescaled together by
+ *              an exact power of two whenever they leave 2^-200 .. 2^200 (looked at every 4 frames) and the exponent e is
+ *              summed in an integer.  logp = log(alpha[n-1][S-1] + alpha[n-1][S-2]) + e ln 2 in double; P = 0 gives -inf.
+ * Outputs, (R,max_units) each: unit_first (index of the unit's first label in its row), unit_len (its label count) int32 and
+ * unit_logp float64; past the row's count first = len = -1 and logp = NaN.  n_units (R) int32 is the TRUE count, which may
+ * exceed max_units: the first max_units are then written and nothing past them is touched.  A unit of more than
+ * DS2_UNIT_MAX_LABELS labels is listed with logp = NaN; dropped (R) int32 counts such units of the row, listed or not.
+ * Checked on the device, not an error: a row is INVALID, with n_units = -1, dropped = 0 and no unit, if lens[r] lies outside
+ * 0..stride, utt[r] outside [0, B), a label outside [0, A) or equal to blank, or the offsets are not strictly increasing inside
+ * [0, min(sizes[utt], T)).
+ * DS2_ERR_ARG before any launch: A outside 1..256; blank outside [0, A); space_id outside -1 .. A-1 or equal to blank; R,
+ * stride or max_units < 1; B or T < 1 or B T > 2^25; R stride or R max_units > 2^27; a NULL pointer (utt may be NULL); a
+ * workspace smaller than ds2_ctc_unit_posterior_ws_bytes(R, stride, max_units) (the message names the needed size).
+ * Nothing outside a unit's span, past sizes[utt], or in a row past its lens is read: all of that may hold NaN.  The workspace
+ * (each listed unit's first frame and frame count) need not be zeroed.  Results are bit-identical from run to run and depend
+ * neither on the other rows, nor on max_units, nor on the workspace's contents.  Two launches on the stream (units, values);
+ * no workgroup waits on another, nothing waits on the stream.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+#define DS2_UNIT_MAX_LABELS 64
+size_t ds2_ctc_unit_posterior_ws_bytes(int R, int stride, int max_units);
+int ds2_ctc_unit_posterior(const float* probs, const int32_t* sizes, int B, int T, int A, const int32_t* labels,
+                           const int32_t* offsets, const int32_t* lens, const int32_t* utt, int R, int stride, int space_id,
+                           int blank, int max_units, void* ws, size_t ws_bytes, int32_t* unit_first, int32_t* unit_len,
+                           double* unit_logp, int32_t* n_units, int32_t* dropped, void* stream);
+
 /* ------------------------------------------------------------------ voice-activity segmentation (csrc/vad.hip)
  * Not in the reference (it cuts its corpora with dataset scripts and sox).  Cuts a recording of any length into the clips the
  * model was trained on, from the int16 samples already on the device.  Integer arithmetic only: a result is exact.

@@ -3,7 +3,10 @@
 checkpoint and report corpus-level WER / CER (``test.py:81-104``: total edits / total reference words, chars).
 Additions: ``--decoder beam`` with ``--lm-path``, ``--hotword`` and ``--nbest N`` (the device search; with ``--nbest`` an
 ``Oracle Summary`` line follows the ``Test Summary``: the best of each utterance's N alternatives, WER and CER
-independently; ``--nbest-path`` writes the alternatives as JSON lines)."""
+independently; ``--nbest-path`` writes the alternatives as JSON lines); ``--confidence-path FILE`` (greedy or beam, the
+device search): one JSON line per utterance with every hypothesis word's span posterior (``codes.confidence``) and whether
+a minimal word alignment to the reference keeps it (``codes.metrics.word_matches``), and a ``Confidence Summary`` line
+after the ``Test Summary``: the data to measure calibration with, which nobody has done for this value."""
 import argparse
 import json
 import os
@@ -50,6 +53,9 @@ def main(argv=None):
     p.add_argument('--nbest-path', default=None, type=str, metavar='FILE',
                    help='with --decoder beam: write one JSON line per utterance, {"reference", "alternatives": [{"text", '
                         '"score", "ctc_logp", "posterior"}]}, for an external rescorer (runs the device search)')
+    p.add_argument('--confidence-path', default=None, type=str, metavar='FILE',
+                   help='with --decoder greedy or beam (runs the device search): write one JSON line per utterance, '
+                        '{"reference", "text", "words": [{"word", "confidence", "correct"}]}')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--output-path', default=None, type=str)
     args = p.parse_args(argv)
@@ -59,6 +65,8 @@ def main(argv=None):
     nbest = check_nbest_arguments(p, args)
     if args.nbest_path and args.decoder != 'beam':
         p.error('--nbest-path needs --decoder beam: only the beam search has alternatives')
+    if args.confidence_path and args.decoder == 'none':
+        p.error('--confidence-path needs --decoder greedy or beam: without a decoder there are no words to score')
 
     ckpt = torch.load(args.model_path, map_location='cpu', weights_only=False)      # read once, for the check and the model
     ckpt_langs = checkpoint_langs(ckpt)
@@ -69,11 +77,19 @@ def main(argv=None):
     model, _, val_t, target_t = load_model(args.model_path, return_transforms=True, data_dir=args.data_dir, ckpt=ckpt)
     model.eval().to('cuda')
     target_t = target_t[0]
-    decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder),
+    confidence = None
+    if args.confidence_path:
+        from codes.confidence import UnitConfidence
+        from codes.metrics import word_matches
+        try:
+            confidence = UnitConfidence(target_t.label_encoder)
+        except ValueError as e:
+            raise SystemExit('test.py: --confidence-path: ' + str(e))
+    decoder = {'greedy': lambda: GreedyDecoder(target_t.label_encoder, confidence=confidence),
                'beam': lambda: BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width),
                'none': lambda: None}[args.decoder]
     want_nbest = args.nbest is not None or bool(args.nbest_path)       # either flag runs the device search
-    if args.decoder == 'beam' and (args.lm_path or args.beam_device or hotwords or want_nbest):
+    if args.decoder == 'beam' and (args.lm_path or args.beam_device or hotwords or want_nbest or args.confidence_path):
         def decoder():
             lm = None
             if args.lm_path:
@@ -81,7 +97,7 @@ def main(argv=None):
                 lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
             booster = booster_from_arguments('test.py', args, target_t) if hotwords else None
             return DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                        beta=args.beta, booster=booster, nbest=nbest)
+                                        beta=args.beta, booster=booster, nbest=nbest, confidence=confidence)
     decoder = decoder()
     target_decoder = GreedyDecoder(target_t.label_encoder)
     dataset = AudioDataset(args.data_dir, args.manifest, transforms=val_t, target_transforms=target_t)
@@ -91,6 +107,7 @@ def main(argv=None):
     total_cer = total_wer = num_tokens = num_chars = 0
     oracle_wer = oracle_cer = 0                     # --nbest: the best alternative per utterance, WER and CER independently
     nbest_lines = []
+    conf_lines, conf_sums = [], {True: [0, 0.0], False: [0, 0.0]}      # correct / wrong: words with a value, their sum
     output_data = []
     for wavs, targets, _, target_sizes in loader:
         inputs, input_percentages = frontend(wavs)
@@ -122,6 +139,16 @@ def main(argv=None):
                     fields = [(transcript, s, decoder.last_ctc_log_probs[i], 1.0 if s > float('-inf') else 0.0)]
                 nbest_lines.append(json.dumps({'reference': reference, 'alternatives': [
                     {'text': t_, 'score': s_, 'ctc_logp': c_, 'posterior': p_} for t_, s_, c_, p_ in fields]}))
+            if confidence is not None:
+                words = transcript.split()
+                values = decoder.last_confidences[i][0]
+                marks = word_matches(words, reference.split())
+                for v, ok in zip(values, marks):
+                    if v is not None:
+                        conf_sums[ok][0] += 1
+                        conf_sums[ok][1] += v
+                conf_lines.append(json.dumps({'reference': reference, 'text': transcript, 'words': [
+                    {'word': w_, 'confidence': v_, 'correct': ok_} for w_, v_, ok_ in zip(words, values, marks)]}))
             if args.verbose:
                 print('Ref: {}\nHyp: {}\nWER: {}\t CER: {}\n'.format(reference.lower(), transcript.lower(),
                                                                       w / max(1, len(reference.split())),
@@ -135,6 +162,12 @@ def main(argv=None):
         if args.nbest_path:
             with open(args.nbest_path, 'w') as f:
                 f.write(''.join(line + '\n' for line in nbest_lines))
+        if confidence is not None:
+            (n_ok, sum_ok), (n_bad, sum_bad) = conf_sums[True], conf_sums[False]
+            print('Confidence Summary \twords {n}\tcorrect {c}\tmean confidence correct {x:.3f}\twrong {y:.3f}\t'.format(
+                n=n_ok + n_bad, c=n_ok, x=sum_ok / max(1, n_ok), y=sum_bad / max(1, n_bad)))
+            with open(args.confidence_path, 'w') as f:
+                f.write(''.join(line + '\n' for line in conf_lines))
     else:
         np.save(args.output_path, np.asarray(output_data, dtype=object), allow_pickle=True)
 

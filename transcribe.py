@@ -4,7 +4,7 @@
     python transcribe.py --model-path CKPT (--audio A.wav [B.wav ...] | --manifest M.csv [--data-dir DIR])
                          --output-path OUT.jsonl [--batch-size 32] [--decoder greedy|beam] [--beam-width W]
                          [--lm-path F --lm-unit U --alpha A --beta B] [--beam-device] [--resample]
-                         [--hotword PHRASE ...] [--hotwords FILE] [--hotword-weight W] [--nbest N]
+                         [--hotword PHRASE ...] [--hotwords FILE] [--hotword-weight W] [--nbest N] [--confidence]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
 
@@ -24,7 +24,10 @@ test.py's.  Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by 
 record gains ``nbest`` and every segment ``alternatives``, a list of ``{text, score, posterior}``, best first, element 0
 being the segment's ``text``; ``words`` and all times stay those of the 1-best, and ``posterior`` is the weight of an
 alternative among the ones returned under the fused score (``codes.decoder.DeviceBeamCTCDecoder``), not a calibrated
-probability."""
+probability.  ``--confidence`` (with ``--decoder beam``: the device search): every entry of ``words`` gains ``confidence``,
+the word's span posterior (``codes.confidence``; include/ds2hip.h "unit posterior") rounded to 4 decimals, or null for a
+word of more than 64 characters; with ``--nbest`` every alternative gains ``word_confidences``, a list in word order.  The
+value is acoustic only, conditional on the frames the decoder gave the word, and nobody has measured its calibration."""
 import argparse
 import json
 import os
@@ -94,8 +97,14 @@ def batch_order(blocks, batch_size):
     return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
 
 
-def segment_record(start_block, end_block, text, offsets):
-    """One entry of ``segments``: times from the segment's blocks (block / 100) and the decoder's per-character offsets."""
+def rounded_confidences(values):
+    """The values as the record prints them: 4 decimals, None staying None."""
+    return [None if c is None else round(float(c), 4) for c in values]
+
+
+def segment_record(start_block, end_block, text, offsets, confidences=None):
+    """One entry of ``segments``: times from the segment's blocks (block / 100) and the decoder's per-character offsets.
+    ``confidences``: one value per word of ``text`` (``--confidence``); every word then gains ``confidence``."""
     t0 = int(start_block) / 100.0
     offs = [int(o) for o in offsets]
     if len(offs) != len(text):
@@ -103,6 +112,11 @@ def segment_record(start_block, end_block, text, offsets):
     sec = ForcedAligner.frame_to_seconds
     words = [{'word': w, 'start': round(t0 + sec(s), 3), 'end': round(t0 + sec(e), 3)}
              for w, s, e in group_words([(c, o, o) for c, o in zip(text, offs)])]
+    if confidences is not None:
+        if len(confidences) != len(words):
+            raise ValueError('%d confidences for %d words' % (len(confidences), len(words)))
+        for word, c in zip(words, rounded_confidences(confidences)):
+            word['confidence'] = c
     return {'start': round(t0, 3), 'end': round(int(end_block) / 100.0, 3), 'text': text, 'words': words}
 
 
@@ -125,10 +139,12 @@ def segment_alternatives(decoder, k, texts, nbest):
     return [{'text': t, 'score': s, 'posterior': p} for t, s, p in zip(texts, scores, post)]
 
 
-def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch_size, device='cuda', nbest=None):
+def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch_size, device='cuda', nbest=None,
+                       confidence=False):
     """``samples``: 1-D int16 numpy array or tensor of one recording -> its JSON record.  One upload, one segmentation and
     one int16 -> float conversion of the whole buffer; every segment is a slice of that buffer.  ``nbest``: the N of
-    ``--nbest`` (a ``DeviceBeamCTCDecoder(nbest=N)``); every segment then gains ``alternatives``."""
+    ``--nbest`` (a ``DeviceBeamCTCDecoder(nbest=N)``); every segment then gains ``alternatives``.  ``confidence``: the
+    decoder was built with a ``UnitConfidence``; words (and alternatives) gain their confidences."""
     from ds2hip import ops
     pcm = torch.as_tensor(samples)
     n = int(pcm.numel())
@@ -143,10 +159,15 @@ def transcribe_samples(path, samples, model, frontend, decoder, segmenter, batch
             out = model(inputs)                                                     # (B,T,A) probabilities
             sizes = input_percentages.mul_(int(out.shape[1])).int()                 # as test.py
             decoded, offsets = decoder.decode(out, sizes)
+            conf = decoder.last_confidences if confidence else None
             for k, i in enumerate(group):
-                entries[i] = segment_record(blocks[i][0], blocks[i][1], decoded[k][0], offsets[k][0].tolist())
+                entries[i] = segment_record(blocks[i][0], blocks[i][1], decoded[k][0], offsets[k][0].tolist(),
+                                            None if conf is None else conf[k][0])
                 if nbest is not None:
                     entries[i]['alternatives'] = segment_alternatives(decoder, k, decoded[k], nbest)
+                    if conf is not None:
+                        for alt, values in zip(entries[i]['alternatives'], conf[k]):
+                            alt['word_confidences'] = rounded_confidences(values)
     return file_record(path, n, stats, entries)
 
 
@@ -172,6 +193,8 @@ def main(argv=None):
                    help='run --decoder beam as one batched device launch (implied by --lm-path)')
     add_hotword_arguments(p)
     add_nbest_arguments(p)
+    p.add_argument('--confidence', action='store_true',
+                   help='add every word\'s span posterior to the record (with --decoder beam: runs the device search)')
     p.add_argument('--max-segment', default=15.0, type=float, help='longest segment in seconds (default: 15)')
     p.add_argument('--min-speech', default=0.25, type=float, help='shorter speech is dropped, seconds (default: 0.25)')
     p.add_argument('--min-silence', default=0.3, type=float, help='shorter gaps are closed, seconds (default: 0.3)')
@@ -221,16 +244,23 @@ def main(argv=None):
     model, _, val_t, target_t = load_model(args.model_path, return_transforms=True, data_dir=args.data_dir, ckpt=ckpt)
     model.eval().to('cuda')
     target_t = target_t[0]
+    confidence = None
+    if args.confidence:
+        from codes.confidence import UnitConfidence
+        try:
+            confidence = UnitConfidence(target_t.label_encoder)
+        except ValueError as e:
+            raise SystemExit('transcribe.py: --confidence: ' + str(e))
     if args.decoder == 'greedy':
-        decoder = GreedyDecoder(target_t.label_encoder)
-    elif args.lm_path or args.beam_device or hotwords or args.nbest is not None:
+        decoder = GreedyDecoder(target_t.label_encoder, confidence=confidence)
+    elif args.lm_path or args.beam_device or hotwords or args.nbest is not None or args.confidence:
         lm = None
         if args.lm_path:
             from codes.lm import NGramLM
             lm = NGramLM.from_arpa(args.lm_path, target_t.label_encoder.classes_.tolist(), unit=args.lm_unit)
         booster = booster_from_arguments('transcribe.py', args, target_t) if hotwords else None
         decoder = DeviceBeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width, lm=lm, alpha=args.alpha,
-                                       beta=args.beta, booster=booster, nbest=nbest)
+                                       beta=args.beta, booster=booster, nbest=nbest, confidence=confidence)
     else:
         decoder = BeamCTCDecoder(target_t.label_encoder, beam_width=args.beam_width)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
@@ -244,7 +274,7 @@ def main(argv=None):
             except ValueError as e:
                 raise SystemExit('transcribe.py: ' + str(e))
             rec = transcribe_samples(name, samples, model, frontend, decoder, segmenter, args.batch_size,
-                                     nbest=args.nbest)
+                                     nbest=args.nbest, confidence=args.confidence)
             rec.update(source)
             if args.nbest is not None:
                 rec['nbest'] = nbest
