@@ -521,9 +521,10 @@ def test_gru_recurrence_fwd_bwd(ops, monkeypatch, mode, t, bsz, n_in, hid):
         np.testing.assert_allclose(dw_hh_r.cpu().numpy(), gru.weight_hh_l0_reverse.grad.numpy(), rtol=1e-4, atol=1e-4)
 
 
-def _persistent_forms_against_step_kernels(ops, monkeypatch, t, bsz, hid, env):
+def _persistent_forms_against_step_kernels(ops, monkeypatch, t, bsz, hid, env, spare_cus=-1, dh=False):
     """One forward and one backward recurrence with the persistent kernels that ``env`` selects, against the launch-per-step
-    kernels on the same inputs."""
+    kernels on the same inputs.  ``dh``: the persistent backward pass is the d(h) hand-off, on the forward pass's own
+    coefficient planes."""
     torch.manual_seed(t + bsz)
     k = 1.0 / hid ** 0.5
     w_hh = ((torch.rand(2, 3 * hid, hid) * 2 - 1) * k).to(DEV)
@@ -536,9 +537,11 @@ def _persistent_forms_against_step_kernels(ops, monkeypatch, t, bsz, hid, env):
         for name, value in env.items():
             monkeypatch.setenv(name, value)
         g = gi.clone()
-        ghn, hout = ops.gru_bidir_fwd(g, w_hh, t, bsz, hid)
+        out = ops.gru_bidir_fwd(g, w_hh, t, bsz, hid, want_coef=dh)
+        ghn, hout, coef = out if dh else out + (None,)
+        assert (coef is not None) == (dh and mode == 'persistent')
         fwd = (g.clone(), ghn.clone(), hout.clone())
-        ops.gru_bidir_bwd(g, ghn, hout, d_out, w_hh_t, t, bsz, hid)
+        ops.gru_bidir_bwd(g, ghn, hout, d_out, w_hh_t, t, bsz, hid, spare_cus=spare_cus, coef=coef)
         torch.cuda.synchronize()
         ops.check_async_errors()
         res[mode] = fwd + (g, ghn)
@@ -570,6 +573,28 @@ def test_gru_persistent_16x16_narrow_widths_agree_with_step_kernels(ops, monkeyp
     tile).  T = 5 uses both ring slots and a steady-state step.  The whole-batch forms with 2 and 4 batch tiles exist in the
     tuning library only and are not run here."""
     _persistent_forms_against_step_kernels(ops, monkeypatch, 5, bsz, hid, dict(env, DS2_GRU_BWD_DH='0'))
+    assert not ops._persistent_off
+
+
+_P4 = {'DS2_GRU_FWD': '4', 'DS2_GRU_BWD': '4'}
+# (id, hid, bsz, env, spare_cus, dh)
+_P4_NARROW = [('h%d-b%d-%s' % (hid, bsz, 'cus%d' % spare if spare >= 0 else 'default'), hid, bsz, _P4, spare, False)
+              for hid in (64, 256, 384) for bsz in (3, 4, 5, 7, 8, 9, 10, 12, 16, 24)
+              for spare in ((0, 52, 82) if 9 <= bsz <= 12 else (-1,))]
+_P4_NARROW += [('h%d-b10-default-narrowfwd' % hid, hid, 10, dict(_P4, DS2_GRU_FWD_WIDE='0'), -1, False) for hid in (64, 256, 384)]
+_P4_NARROW += [('h64-b%d-cus52-dh' % bsz, 64, bsz, dict(_P4, DS2_GRU_BWD_DH='1'), 52, True) for bsz in (9, 10, 12)]
+
+
+@pytest.mark.parametrize('hid,bsz,env,spare_cus,dh', [c[1:] for c in _P4_NARROW], ids=[c[0] for c in _P4_NARROW])
+def test_gru_persistent_4x4_narrow_widths_agree_with_step_kernels(ops, monkeypatch, hid, bsz, env, spare_cus, dh):
+    """The instantiations of the 4x4x1 kernels (gru_persist.hip) that the H = 800 cases do not reach: these three widths run
+    backward k groups per wave (NGI) 1, 2, 3 and forward NGI 1.  B = 3, 4: one part, speculative (backward NRG = 2, forward
+    P = 1); 5, 7, 8: two parts (3 / 2, 4 / 3, 4 / 4 rows), the backward broadcast deal with NRG = 4 and forward P = 2;
+    9, 10, 12: three parts of 3 / 3 / 3, 4 / 4 / 2 and 4 / 4 / 4 rows, the broadcast deal with 20, 24 and 28 units by spare_cus (NRG = 5, 6, 7) and the forward
+    20-unit form (UGX = 5; 24 units with DS2_GRU_FWD_WIDE=0); 16 and 24: the counted protocol, backward NRG = 4 and 6, forward
+    two batch-row passes (NBT = 2).  The d(h) hand-off exists at H = 64 and 800 only: its 24-unit form at H = 64, which the
+    short-sequence d(h) test (spare_cus 0 and 82) does not reach.  T = 5 uses every ring slot and a steady-state step."""
+    _persistent_forms_against_step_kernels(ops, monkeypatch, 5, bsz, hid, dict({'DS2_GRU_BWD_DH': '0'}, **env), spare_cus, dh)
     assert not ops._persistent_off
 
 
