@@ -113,6 +113,15 @@ def band_margin(states, lo, W, S):
     return min(found) if found else None
 
 
+def path_band(states, W, S):
+    """The band that follows a state path: int64 ``lo = cummax(clamp(states - W//2, 0, max(S - W, 0)))``, integers only.  A
+    path never falls and moves at most two states per frame, so this lo is non-negative, non-decreasing, rises by at most 2
+    (< W) per frame and holds the path itself: a legal band, centred on the path wherever the ends of the state row let it."""
+    states = torch.as_tensor(states).to(torch.int64).reshape(-1)
+    lo = (states - int(W) // 2).clamp_(min=0).clamp_(max=max(int(S) - int(W), 0))
+    return torch.cummax(lo, 0)[0] if lo.numel() else lo
+
+
 class LongAligner(ForcedAligner):
     """Alignment of ONE long recording's probabilities to its whole transcript with ``ds2_ctc_align_banded`` on a diagonal
     band.  ``align(probs (T,A) on the device, labels)`` starts at the smallest band the library takes that is at least
@@ -120,13 +129,45 @@ class LongAligner(ForcedAligner):
     path comes closer than ``band_margin`` states to a restricting edge, until the band holds all S states or is the
     library's widest; the last attempt is returned as it is: ``score``, ``score_per_frame``, ``chars``, ``words`` (as
     ``ForcedAligner``), ``states`` (int32 tensor (T,) on the device, -1 without an alignment), ``band_states`` (the width
-    used) and ``band_margin`` (``band_margin()`` of the path; None without an alignment or a restricting edge)."""
+    used) and ``band_margin`` (``band_margin()`` of the path; None without an alignment or a restricting edge).
 
-    def __init__(self, label_encoder, band_states=4096, band_margin=16, blank_index=0, log_input=False):
+    ``gap_penalty`` (None: everything above, nothing else) aligns with ``ds2_ctc_align_banded_gap`` instead: the blanks
+    between words may absorb audio the transcript does not cover, at ``gap_penalty`` nats per frame below the frame's best
+    symbol.  ``space_index`` defaults to the label encoder's ``' '``, or -1 (end blanks only) if the alphabet has none.  A long
+    uncovered opening moves the true path off the diagonal by more than half a band, and a diagonal band of any legal width
+    then clips it; so if the doubling ends still tight with a finite score, up to ``recentre`` further launches at the same
+    width use ``path_band(previous states)``, stopping at the first that is not tight.  The result gains ``gap`` (uint8
+    tensor (T,) on the device: the frames the path absorbed), ``gap_frames`` and ``band_recentred`` (the number of such
+    launches)."""
+
+    def __init__(self, label_encoder, band_states=4096, band_margin=16, blank_index=0, log_input=False, gap_penalty=None,
+                 space_index=None, recentre=2):
         super().__init__(label_encoder, blank_index, log_input)
         self.band_states, self.band_margin = int(band_states), int(band_margin)
         if self.band_states < 1:
             raise ValueError('LongAligner: band_states = %r is not a positive number of states' % (band_states,))
+        self.gap_penalty = None if gap_penalty is None else float(gap_penalty)
+        if self.gap_penalty is not None and not self.gap_penalty >= 0:
+            raise ValueError('LongAligner: gap_penalty = %r is negative or not a number' % (gap_penalty,))
+        if space_index is None:
+            space_index = getattr(self.label_encoder, 'map_classes_', {}).get(' ', -1)
+        self.space_index, self.recentre = int(space_index), int(recentre)
+
+    def _launch(self, p, t_n, labels_d, n, lo, width):
+        """One launch on the band ``lo`` -> (states, starts, ends, gap or None, score, margin, tight)."""
+        dev = p.device
+        i32 = lambda v: torch.tensor([v], dtype=torch.int32, device=dev)    # noqa: E731
+        args = (p, i32(t_n), labels_d, i32(0), i32(n), n, lo.to(dev, torch.int32)[None], width)
+        if self.gap_penalty is None:
+            states, starts, ends, score = ops.ctc_align_banded(*args, self.blank_index, self.log_input)
+            gap = None
+        else:
+            states, starts, ends, gap, score = ops.ctc_align_banded_gap(*args, self.space_index, self.gap_penalty,
+                                                                        self.blank_index, self.log_input)
+        sc = float(score[0])
+        margin = band_margin(states[0], lo, width, 2 * n + 1) if math.isfinite(sc) and t_n else None
+        tight = not math.isfinite(sc) or (margin is not None and margin < self.band_margin)
+        return states, starts, ends, gap, sc, margin, tight
 
     def align(self, probs, labels):
         if not probs.is_cuda:
@@ -137,21 +178,23 @@ class LongAligner(ForcedAligner):
         labels_h = torch.as_tensor(np.asarray(labels, dtype=np.int64).reshape(-1)).to(torch.int32)
         n = int(labels_h.numel())
         s_n = 2 * n + 1
-        i32 = lambda v: torch.tensor([v], dtype=torch.int32, device=dev)    # noqa: E731
         p, labels_d = probs.detach().contiguous().float()[None], labels_h.to(dev)
         width = max(lib.ALIGN_BAND_MIN, 1 << max(min(s_n, self.band_states) - 1, 0).bit_length())
         width = min(width, lib.ALIGN_BAND_MAX)
         while True:
-            lo = diagonal_band(t_n, s_n, width)
-            states, starts, ends, score = ops.ctc_align_banded(
-                p, i32(t_n), labels_d, i32(0), i32(n), n, lo.to(dev, torch.int32)[None], width, self.blank_index,
-                self.log_input)
-            sc = float(score[0])
-            margin = band_margin(states[0], lo, width, s_n) if math.isfinite(sc) and t_n else None
-            tight = not math.isfinite(sc) or (margin is not None and margin < self.band_margin)
+            states, starts, ends, gap, sc, margin, tight = self._launch(p, t_n, labels_d, n, diagonal_band(t_n, s_n, width),
+                                                                        width)
             if not tight or width >= s_n or width >= lib.ALIGN_BAND_MAX:
                 break
             width *= 2
+        recentred = 0
+        while self.gap_penalty is not None and tight and math.isfinite(sc) and recentred < self.recentre:
+            states, starts, ends, gap, sc, margin, tight = self._launch(p, t_n, labels_d, n,
+                                                                        path_band(states[0], width, s_n), width)
+            recentred += 1
         chars = self._chars(labels_h.numpy(), starts[0].cpu().numpy(), ends[0].cpu().numpy()) if math.isfinite(sc) else []
-        return {'score': sc, 'score_per_frame': sc / max(t_n, 1), 'chars': chars, 'words': group_words(chars),
-                'states': states[0], 'band_states': width, 'band_margin': margin}
+        res = {'score': sc, 'score_per_frame': sc / max(t_n, 1), 'chars': chars, 'words': group_words(chars),
+               'states': states[0], 'band_states': width, 'band_margin': margin}
+        if self.gap_penalty is not None:
+            res.update(gap=gap[0], gap_frames=int(gap[0].sum()), band_recentred=recentred)
+        return res

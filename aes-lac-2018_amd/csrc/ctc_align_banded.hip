@@ -22,6 +22,17 @@
 //   score       float64: an hour's path score is about -1e5.
 // Score rows: 2 x W doubles of dynamic LDS (128 KiB at W = 8192; the static part is 17 KiB).  Back-trace as in ctc_align.hip.
 // Critical path: T barriers per utterance, then T dependent LDS reads of one thread.
+//
+// GAP = true is ds2_ctc_align_banded_gap (include/ds2hip.h, "banded CTC alignment with gaps"): the same states, band, scores
+// and ties; only the EMISSION of the eligible blank states (the two end blanks and the blanks beside a space label) differs:
+// it is max(lp[t][blank], f[t]) with f[t] = max_a lp[t][a] - gap_penalty, and a frame where f[t] wins strictly is a gap frame.
+//   mrow        f[t] of the staged chunk's frames, computed from the chunk's emissions in LDS once per chunk, 8 lanes per
+//               frame (one more barrier per chunk, none per frame); every thread reads the frame's value as a broadcast.
+//   eligibility bit 9 of symskip[k], set with the symbol when the slot takes over a state (a blank slot then reads the two
+//               labels beside it, where the plain form reads none).
+//   gap flag    bit 2 of the back-pointer byte (code | gap << 2), written by the recursion; the back-trace steps by
+//               (byte & 3) and writes gap[t] from the byte of the state it walks through.
+// The GAP = false instantiations contain none of this.
 #include "ds2_common.h"
 
 namespace {
@@ -35,16 +46,19 @@ constexpr int BT_F = 64;                 // back-trace: frames per window
 constexpr int BT_W = 2 * BT_F;           // ... and states per window row (the walk needs 2 (BT_F - 1) + 1)
 #define NEG_INF_D (-(double)INFINITY)
 
-template <int W, int NTHR, int K>
+template <int W, int NTHR, int K, bool GAP>
 __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
     const float* __restrict__ probs, const int32_t* __restrict__ sizes, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ label_lens, const int32_t* __restrict__ lo_all,
     int T, int A, int lmax, int blank, int log_input, uint8_t* bp_all, int32_t* __restrict__ states,
-    int32_t* __restrict__ starts, int32_t* __restrict__ ends, double* __restrict__ score) {
+    int32_t* __restrict__ starts, int32_t* __restrict__ ends, double* __restrict__ score, int space, float gap_penalty,
+    uint8_t* __restrict__ gap_all) {
     static_assert(NTHR * K == W || (K == 1 && NTHR > W), "every slot has one owner");
     extern __shared__ double rowbuf[];   // [2][W], slot = state mod W
     __shared__ float em[2][EM_FLOATS];
     __shared__ int lo_s[2][MAX_CH];
+    __shared__ float mrow[GAP ? 2 : 1][GAP ? MAX_CH : 1];   // GAP: f[t] = max_a lp[t][a] - gap_penalty of the staged frames
+    __shared__ uint8_t pgap[GAP ? BT_F : 1];                // GAP: the gap flag of the path's frames in a back-trace window
     __shared__ uint8_t win[BT_F][BT_W];
     __shared__ int path[BT_F + 2];       // path[1 + f] = state at frame t_lo + f; [0] / [n + 1] = the frames around the window
     __shared__ int bad;
@@ -71,14 +85,18 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
     int32_t* st_out = states + (size_t)b * T;
     int32_t* start_out = starts + (size_t)b * lmax;
     int32_t* end_out = ends + (size_t)b * lmax;
-    for (int t = tl + tid; t < T; t += NTHR) st_out[t] = -1;
+    uint8_t* gap_out = GAP ? gap_all + (size_t)b * T : nullptr;
+    for (int t = tl + tid; t < T; t += NTHR) {
+        st_out[t] = -1;
+        if constexpr (GAP) gap_out[t] = 0;
+    }
     for (int l = L + tid; l < lmax; l += NTHR) start_out[l] = end_out[l] = -1;
 
     uint8_t* bp = bp_all + (size_t)b * T * W;
     double final_v = NEG_INF_D;
     int final_s = -1;
     if (!bad && tl > 0) {
-        int held[K], symskip[K];                            // the state each owned slot holds; its symbol | skip << 8
+        int held[K], symskip[K];                            // the state each owned slot holds; its symbol | skip << 8 | eligible << 9
 #pragma unroll
         for (int k = 0; k < K; ++k) held[k] = -1, symskip[k] = 0;
         // staging roles: thread tid < 256 carries elements idx = tid + 256 i of a chunk (CH frames of A floats, contiguous),
@@ -122,6 +140,23 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
             const bool more = c + 1 < nchunk;
             if (more) stage_load(c + 1);                    // in flight while this chunk's frames are worked on
             const int fend = min(CH, tl - c * CH);
+            if constexpr (GAP) {
+                // (the chunk's emissions are behind the barrier that ended the last chunk; mrow[c & 1]'s last readers were in
+                // chunk c - 2)
+                // 8 lanes per frame (threads 0..255 are four whole waves at every NTHR), then an xor butterfly: one thread per
+                // frame would put A dependent LDS reads in front of the chunk's first frame (measured: DESIGN.md)
+                if (tid < 8 * MAX_CH) {
+                    const int r = tid >> 3, part = tid & 7;
+                    float m = -INFINITY;                    // (no NaN in em)
+                    if (r < fend)
+                        for (int a = part; a < A; a += 8) m = fmaxf(m, em[c & 1][r * A + a]);
+                    m = fmaxf(m, __shfl_xor(m, 1));
+                    m = fmaxf(m, __shfl_xor(m, 2));
+                    m = fmaxf(m, __shfl_xor(m, 4));
+                    if (part == 0 && r < fend) mrow[c & 1][r] = (m == -INFINITY) ? -INFINITY : m - gap_penalty;
+                }
+                __syncthreads();
+            }
             for (int f = 0; f < fend; ++f) {
                 const int lo_t = lo_s[c & 1][f];
                 if (lo_t < lo_prev || lo_t >= S || lo_t - lo_prev >= W) {   // the same value in every thread: all leave together
@@ -131,6 +166,8 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                 const double* prev = rowbuf + cur * W;
                 double* nxt = rowbuf + (cur ^ 1) * W;
                 const float* e = em[c & 1] + f * A;
+                float fgap = 0.f;
+                if constexpr (GAP) fgap = mrow[c & 1][f];
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const int j = tid + NTHR * k;
@@ -138,20 +175,27 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                     if ((NTHR <= W || j < W) && su < (unsigned)S) {
                         const int s = (int)su;
                         if (s != held[k]) {
-                            int sym = blank, skip = 0;
+                            int sym = blank, skip = 0, elig = 0;
                             if (s & 1) {
                                 sym = lab[s >> 1];
                                 skip = s >= 3 && sym != lab[(s >> 1) - 1];
+                            } else if constexpr (GAP) {     // (0 < s < 2 L: labels s/2 - 1 and s/2 both exist)
+                                elig = s == 0 || s == S - 1 || lab[(s >> 1) - 1] == space || lab[s >> 1] == space;
                             }
                             held[k] = s;
-                            symskip[k] = sym | (skip << 8);
+                            symskip[k] = sym | (skip << 8) | (elig << 9);
                         }
                         const int d = s - lo_prev;          // >= 0; the predecessor s - i is in frame t-1's band iff d - i is in 0..W-1
                         const double r0 = prev[j], r1 = prev[(j - 1) & (W - 1)], r2 = prev[(j - 2) & (W - 1)];
-                        const float ev = e[symskip[k] & 255];
+                        float ev = e[symskip[k] & 255];
+                        int gapf = 0;
+                        if constexpr (GAP) {
+                            gapf = ((symskip[k] >> 9) & 1) && fgap > ev;            // strict, in fp32
+                            ev = gapf ? fgap : ev;
+                        }
                         const double x0 = (unsigned)d < (unsigned)W ? r0 : NEG_INF_D;
                         const double x1 = (unsigned)(d - 1) < (unsigned)W ? r1 : NEG_INF_D;
-                        const double x2 = ((symskip[k] >> 8) && (unsigned)(d - 2) < (unsigned)W) ? r2 : NEG_INF_D;
+                        const double x2 = (((symskip[k] >> 8) & (GAP ? 1 : -1)) && (unsigned)(d - 2) < (unsigned)W) ? r2 : NEG_INF_D;
                         double best = x0;
                         int code = 0;
                         if (x1 > best) {
@@ -163,7 +207,7 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                             code = 2;
                         }
                         nxt[j] = (best == NEG_INF_D) ? NEG_INF_D : best + (double)ev;
-                        bp[(size_t)t * W + j] = (uint8_t)code;
+                        bp[(size_t)t * W + j] = (uint8_t)(GAP ? code | (gapf << 2) : code);
                     }
                 }
                 if (more && f == fend - 1) stage_store((c + 1) & 1);    // (its last readers passed chunk c - 1's final barrier)
@@ -192,7 +236,10 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
     if (tid == 0) score[b] = final_v == final_v ? final_v : NEG_INF_D;
     const bool feasible = final_v != NEG_INF_D && final_v == final_v;
     if (!feasible || tl == 0) {
-        for (int t = tid; t < tl; t += NTHR) st_out[t] = -1;
+        for (int t = tid; t < tl; t += NTHR) {
+            st_out[t] = -1;
+            if constexpr (GAP) gap_out[t] = 0;
+        }
         for (int l = tid; l < L; l += NTHR) start_out[l] = end_out[l] = -1;
         return;
     }
@@ -215,7 +262,11 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
             path[n + 1] = after;
             for (int f = n - 1; f >= 0; --f) {
                 path[1 + f] = w;
-                const int code = win[f][max(w - s_lo, 0)];  // (w >= s_hi - 2 (n - 1 - f) >= s_lo on a path; the clamp is for the index only)
+                int code = win[f][max(w - s_lo, 0)];        // (w >= s_hi - 2 (n - 1 - f) >= s_lo on a path; the clamp is for the index only)
+                if constexpr (GAP) {
+                    pgap[f] = (uint8_t)((code >> 2) & 1);
+                    code &= 3;
+                }
                 w = max(w - min(code, 2), 0);               // the step below row 0 may leave the window: it is the next one's top
             }
             path[0] = t_lo > 0 ? w : -2;
@@ -224,6 +275,7 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
         for (int f = tid; f < n; f += NTHR) {
             const int w = path[1 + f], t = t_lo + f;
             st_out[t] = w;
+            if constexpr (GAP) gap_out[t] = pgap[f];
             if (w & 1) {
                 if (path[f] != w) start_out[w >> 1] = t;
                 if (path[2 + f] != w) end_out[w >> 1] = t;
@@ -235,20 +287,91 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
     }
 }
 
-template <int W, int NTHR, int K>
-int launch(int B, hipStream_t st, const float* probs, const int32_t* sizes, const int32_t* labels,
+template <int W, int NTHR, int K, bool GAP>
+int launch(const char* fn, int B, hipStream_t st, const float* probs, const int32_t* sizes, const int32_t* labels,
            const int32_t* label_offsets, const int32_t* label_lens, const int32_t* lo, int T, int A, int lmax, int blank,
-           int log_input, uint8_t* ws, int32_t* states, int32_t* starts, int32_t* ends, double* score) {
-    auto kernel = ctc_align_banded_kernel<W, NTHR, K>;
+           int log_input, uint8_t* ws, int32_t* states, int32_t* starts, int32_t* ends, double* score, int space,
+           float gap_penalty, uint8_t* gap) {
+    auto kernel = ctc_align_banded_kernel<W, NTHR, K, GAP>;
     const size_t dyn = (size_t)2 * W * sizeof(double);
     if (dyn + 20 * 1024 > 64 * 1024 &&                      // (the static part is 17 KiB)
         hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) !=
             hipSuccess) {
-        ds2_set_error("ds2_ctc_align_banded: %zu bytes of dynamic LDS are not available (band %d)", dyn, W);
+        ds2_set_error("%s: %zu bytes of dynamic LDS are not available (band %d)", fn, dyn, W);
         return DS2_ERR_LAUNCH;
     }
     hipLaunchKernelGGL(kernel, dim3(B), dim3(NTHR), dyn, st, probs, sizes, labels, label_offsets, label_lens, lo, T, A, lmax,
-                       blank, log_input, ws, states, starts, ends, score);
+                       blank, log_input, ws, states, starts, ends, score, space, gap_penalty, gap);
+    return DS2_OK;
+}
+
+// the checks and the dispatch of both entry points; GAP picks the instantiation, fn names the entry in messages
+template <bool GAP>
+int run(const char* fn, const float* probs, const int32_t* sizes, const int32_t* labels, const int32_t* label_offsets,
+        const int32_t* label_lens, const int32_t* lo, int B, int T, int A, int max_label_len, int band, int blank, int space,
+        float gap_penalty, int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts, int32_t* ends,
+        uint8_t* gap, double* score, void* stream) {
+#define BANDED_CHECK_ARG(cond)                                      /* DS2_CHECK_ARG under the entry point's name */ \
+    do {                                                                                                            \
+        if (!(cond)) {                                                                                              \
+            ds2_set_error("%s: bad argument: %s", fn, #cond);                                                       \
+            return DS2_ERR_ARG;                                                                                     \
+        }                                                                                                           \
+    } while (0)
+    if (band < BAND_MIN || band > BAND_MAX || (band & (band - 1)) != 0) {
+        ds2_set_error("%s: band %d is not a power of two in %d..%d", fn, band, BAND_MIN, BAND_MAX);
+        return DS2_ERR_ARG;
+    }
+    if (max_label_len < 0 || max_label_len > (INT32_MAX - 1) / 2) {
+        ds2_set_error("%s: max_label_len %d is outside 0..%d (2 L + 1 states are counted in an int32)", fn, max_label_len,
+                      (INT32_MAX - 1) / 2);
+        return DS2_ERR_ARG;
+    }
+    if (A < 1 || A > MAX_A) {
+        ds2_set_error("%s: alphabet size %d is outside 1..%d", fn, A, MAX_A);
+        return DS2_ERR_ARG;
+    }
+    BANDED_CHECK_ARG(B >= 0 && T >= 0 && blank >= 0 && blank < A);
+    if (GAP && !(gap_penalty >= 0.f)) {                     // (a NaN fails the comparison)
+        ds2_set_error("%s: gap_penalty %g is negative or NaN", fn, (double)gap_penalty);
+        return DS2_ERR_ARG;
+    }
+    if (GAP && (space < -1 || space >= A || space == blank)) {
+        ds2_set_error("%s: space %d is neither -1 nor a symbol of 0..%d other than blank %d", fn, space, A - 1, blank);
+        return DS2_ERR_ARG;
+    }
+    if (B == 0) return DS2_OK;
+    // (labels may be NULL when every transcript is empty: it is read only below a positive label_lens[b])
+    BANDED_CHECK_ARG(sizes && label_offsets && label_lens && score && (probs || T == 0) && (lo || T == 0));
+    BANDED_CHECK_ARG((states || T == 0) && ((starts && ends) || max_label_len == 0) && (!GAP || gap || T == 0));
+    if (ws_bytes < ds2_ctc_align_banded_ws_bytes(B, T, band) || !ws) {
+        ds2_set_error("%s: workspace of %zu bytes < %s_ws_bytes = %zu", fn, ws_bytes, fn,
+                      ds2_ctc_align_banded_ws_bytes(B, T, band));
+        return DS2_ERR_ARG;
+    }
+    int rc = DS2_OK;
+#define DS2_BANDED(W_, N_, K_)                                                                                         \
+    rc = launch<W_, N_, K_, GAP>(fn, B, (hipStream_t)stream, probs, sizes, labels, label_offsets, label_lens, lo, T, A, \
+                                 max_label_len, blank, log_input, (uint8_t*)ws, states, starts, ends, score, space,    \
+                                 gap_penalty, gap)
+    switch (band) {
+        case 64: DS2_BANDED(64, 256, 1); break;
+        case 128: DS2_BANDED(128, 256, 1); break;
+        case 256: DS2_BANDED(256, 256, 1); break;
+        case 512: DS2_BANDED(512, 512, 1); break;
+        case 1024: DS2_BANDED(1024, 1024, 1); break;
+        case 2048: DS2_BANDED(2048, 1024, 2); break;
+        case 4096: DS2_BANDED(4096, 1024, 4); break;
+        default: DS2_BANDED(8192, 1024, 8); break;
+    }
+#undef DS2_BANDED
+#undef BANDED_CHECK_ARG
+    if (rc != DS2_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        ds2_set_error("%s: launch failed: %s", fn, hipGetErrorString(e));
+        return DS2_ERR_LAUNCH;
+    }
     return DS2_OK;
 }
 
@@ -263,45 +386,20 @@ extern "C" int ds2_ctc_align_banded(const float* probs, const int32_t* sizes, co
                                     const int32_t* label_offsets, const int32_t* label_lens, const int32_t* lo, int B, int T,
                                     int A, int max_label_len, int band, int blank, int log_input, void* ws, size_t ws_bytes,
                                     int32_t* states, int32_t* starts, int32_t* ends, double* score, void* stream) {
-    if (band < BAND_MIN || band > BAND_MAX || (band & (band - 1)) != 0) {
-        ds2_set_error("ds2_ctc_align_banded: band %d is not a power of two in %d..%d", band, BAND_MIN, BAND_MAX);
-        return DS2_ERR_ARG;
-    }
-    if (max_label_len < 0 || max_label_len > (INT32_MAX - 1) / 2) {
-        ds2_set_error("ds2_ctc_align_banded: max_label_len %d is outside 0..%d (2 L + 1 states are counted in an int32)",
-                      max_label_len, (INT32_MAX - 1) / 2);
-        return DS2_ERR_ARG;
-    }
-    if (A < 1 || A > MAX_A) {
-        ds2_set_error("ds2_ctc_align_banded: alphabet size %d is outside 1..%d", A, MAX_A);
-        return DS2_ERR_ARG;
-    }
-    DS2_CHECK_ARG(B >= 0 && T >= 0 && blank >= 0 && blank < A);
-    if (B == 0) return DS2_OK;
-    // (labels may be NULL when every transcript is empty: it is read only below a positive label_lens[b])
-    DS2_CHECK_ARG(sizes && label_offsets && label_lens && score && (probs || T == 0) && (lo || T == 0));
-    DS2_CHECK_ARG((states || T == 0) && ((starts && ends) || max_label_len == 0));
-    if (ws_bytes < ds2_ctc_align_banded_ws_bytes(B, T, band) || !ws) {
-        ds2_set_error("ds2_ctc_align_banded: workspace of %zu bytes < ds2_ctc_align_banded_ws_bytes = %zu", ws_bytes,
-                      ds2_ctc_align_banded_ws_bytes(B, T, band));
-        return DS2_ERR_ARG;
-    }
-    int rc = DS2_OK;
-#define DS2_BANDED(W_, N_, K_)                                                                                         \
-    rc = launch<W_, N_, K_>(B, (hipStream_t)stream, probs, sizes, labels, label_offsets, label_lens, lo, T, A,          \
-                            max_label_len, blank, log_input, (uint8_t*)ws, states, starts, ends, score)
-    switch (band) {
-        case 64: DS2_BANDED(64, 256, 1); break;
-        case 128: DS2_BANDED(128, 256, 1); break;
-        case 256: DS2_BANDED(256, 256, 1); break;
-        case 512: DS2_BANDED(512, 512, 1); break;
-        case 1024: DS2_BANDED(1024, 1024, 1); break;
-        case 2048: DS2_BANDED(2048, 1024, 2); break;
-        case 4096: DS2_BANDED(4096, 1024, 4); break;
-        default: DS2_BANDED(8192, 1024, 8); break;
-    }
-#undef DS2_BANDED
-    if (rc != DS2_OK) return rc;
-    DS2_CHECK_LAUNCH();
-    return DS2_OK;
+    return run<false>("ds2_ctc_align_banded", probs, sizes, labels, label_offsets, label_lens, lo, B, T, A, max_label_len, band,
+                      blank, -1, 0.f, log_input, ws, ws_bytes, states, starts, ends, nullptr, score, stream);
+}
+
+// the gap form keeps the same back-pointer bytes (the gap flag is a spare bit of each), so the same workspace
+extern "C" size_t ds2_ctc_align_banded_gap_ws_bytes(int B, int T, int band) {
+    return ds2_ctc_align_banded_ws_bytes(B, T, band);
+}
+
+extern "C" int ds2_ctc_align_banded_gap(const float* probs, const int32_t* sizes, const int32_t* labels,
+                                        const int32_t* label_offsets, const int32_t* label_lens, const int32_t* lo, int B,
+                                        int T, int A, int max_label_len, int band, int blank, int space, float gap_penalty,
+                                        int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts,
+                                        int32_t* ends, uint8_t* gap, double* score, void* stream) {
+    return run<true>("ds2_ctc_align_banded_gap", probs, sizes, labels, label_offsets, label_lens, lo, B, T, A, max_label_len,
+                     band, blank, space, gap_penalty, log_input, ws, ws_bytes, states, starts, ends, gap, score, stream);
 }

@@ -106,6 +106,9 @@ SIGNATURES = {
     'ds2_ctc_align': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     'ds2_ctc_align_banded_ws_bytes': (_Z, [_I, _I, _I]),
     'ds2_ctc_align_banded': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    'ds2_ctc_align_banded_gap_ws_bytes': (_Z, [_I, _I, _I]),
+    'ds2_ctc_align_banded_gap': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P,
+                                      _P]),
     'ds2_ctc_keyword_search_ws_bytes': (_Z, [_I, _I]),
     'ds2_ctc_keyword_search': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P]),
     'ds2_ctc_unit_posterior_ws_bytes': (_Z, [_I, _I, _I]),

@@ -1243,6 +1243,32 @@ def ctc_align_banded(probs, sizes, labels, label_offsets, label_lens, max_label_
     return states, starts, ends, score
 
 
+def ctc_align_banded_gap(probs, sizes, labels, label_offsets, label_lens, max_label_len, lo, band, space, gap_penalty, blank=0,
+                         log_input=False):
+    """``ctc_align_banded`` in which the blank states between words (the two end blanks and the blanks beside a ``space``
+    label; ``space`` = -1: the end blanks only) may absorb a frame at ``gap_penalty`` (fp32, >= 0, inf allowed) below the
+    frame's best symbol (``ds2_ctc_align_banded_gap``; include/ds2hip.h has the definition).  Arguments as
+    ``ctc_align_banded``.  Returns the device tensors states, starts, ends, gap (B,T) uint8 -- 1 where the path's frame was
+    absorbed -- and score (B,) FLOAT64.  Nothing waits on the stream."""
+    for x in (probs, sizes, labels, label_offsets, label_lens, lo):
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+    bsz, t, a = probs.shape
+    if lo.dtype != torch.int32 or tuple(lo.shape) != (bsz, t):
+        raise RuntimeError('ctc_align_banded_gap: lo must be int32 of shape (B,T) = (%d,%d)' % (bsz, t))
+    max_label_len, band = int(max_label_len), int(band)
+    ws_bytes = lib.query('ds2_ctc_align_banded_gap_ws_bytes', bsz, t, band)
+    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
+    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
+    ends = torch.empty_like(starts)
+    gap = torch.empty((bsz, t), dtype=torch.uint8, device=probs.device)
+    score = torch.empty((bsz,), dtype=torch.float64, device=probs.device)
+    lib.call('ds2_ctc_align_banded_gap', probs, sizes, labels, label_offsets, label_lens, lo, bsz, t, a, max_label_len, band,
+             int(blank), int(space), float(gap_penalty), int(bool(log_input)), ws, ws.numel(), states, starts, ends, gap, score)
+    return states, starts, ends, gap, score
+
+
 def keyword_search(logp, sizes, labels, label_offsets, label_lens, min_score, max_hits=4, blank=0, ws=None):
     """Where each of K keywords was said in each utterance, in one call on the current stream (``ds2_ctc_keyword_search``;
     include/ds2hip.h has the definition).  logp (B,T,A) fp32 LOG-probabilities on the device; sizes (B,), flat labels,

@@ -4,7 +4,7 @@ reference, whose data scripts only consume corpora that somebody already cut).
 
     python align_long.py --model-path CKPT (--audio A.wav [B.wav ...] --transcript A.txt [B.txt ...] |
                          --manifest M.csv [--data-dir DIR]) --output-path OUT.jsonl [--batch-size 32]
-                         [--band-states 4096 --band-margin 16] [--resample]
+                         [--band-states 4096 --band-margin 16] [--resample] [--gap-penalty G [--max-gap-seconds X]]
                          [--clips-dir DIR --clips-manifest FILE --min-score-per-frame X]
                          [--max-segment S --min-speech S --min-silence S --pad S --percentile Q --margin-db D
                           --min-db D --max-db D]
@@ -28,8 +28,27 @@ segment's start plus the centre of model output step j).
 clean, has a text and scores at or above X as ``DIR/<audio stem>_<k:05d>.wav`` (its int16 samples, bit for bit) and ``.txt``
 (its text), and a manifest row ``wav,txt,duration`` per clip, with paths relative to ``--data-dir`` where that is given: the
 format ``codes.data.AudioDataset`` reads.  There is NO default threshold: nobody has measured what value separates good clips
-from bad on a trained model.  Audio that the transcript does not cover (announcements, music) is force-aligned all the same
-and shows up only as low segment scores; skipping audio or text, resampling and other sample formats are out of scope.
+from bad on a trained model.
+
+``--gap-penalty G`` (default: off) lets the alignment skip audio the transcript does not cover -- announcements, questions
+from the floor, music with voice: the blanks between words (and before the first and after the last) may absorb a frame
+whatever the model says about it, at G nats per absorbed frame below the frame's best symbol
+(``ds2_ctc_align_banded_gap``).  G is a placeholder: nobody has measured which value separates uncovered audio from badly
+recognised covered audio on a trained model.  Without the flag such audio is force-aligned all the same and shows up only as
+low segment scores.  With it:
+  record    gains ``gap_penalty``, ``gap_seconds`` (0.02 s per absorbed frame), ``band_recentred`` (the launches on a band
+            re-centred on the previous path, which a long uncovered opening needs) and ``gaps``, a list of ``{start, end,
+            segment}``: the maximal runs of absorbed frames, cut at segment borders, from the first frame's time to the
+            last's by the same frame-to-seconds rule as words.  Its ``score_per_frame`` stays the kernel's total over ALL
+            frames, the absorbed frames' terms included.
+  segment   gains ``gap_frames``; its ``score_per_frame`` is taken over its NON-gap frames only -- the float64 sum of the
+            path's fp32 logs at those frames over their number, null if it has none -- because a clip threshold judges how
+            the transcript fits the audio it covers.
+  clips     a clip is written only if, beyond the conditions above, ``gap_frames * 0.02 <= --max-gap-seconds`` (default 0:
+            no absorbed frame inside a clip).  A wholly uncovered segment has no text and is never written.
+``--max-gap-seconds`` without ``--gap-penalty`` is refused by name.  Without ``--gap-penalty`` the records and the clips are
+byte for byte what they were before the flag existed.  Skipping TEXT the audio does not contain (headers, footnotes), a
+penalty per position, gaps inside words, resampling beyond ``--resample`` and other sample formats are out of scope.
 Input is 16-bit mono PCM WAV at 16 kHz; anything else is refused by name before any work is done -- unless ``--resample``
 is given, as in transcribe.py: a 16-bit PCM WAV of any supported rate and 1..8 channels is converted to 16 kHz mono on the
 device before it is segmented, the record gains ``source_rate`` and ``source_channels``, every time refers to the 16 kHz
@@ -50,6 +69,9 @@ sys.path.insert(0, ROOT)
 
 from codes.align import ForcedAligner, LongAligner  # noqa: E402
 from transcribe import SAMPLE_RATE, batch_order, read_pcm16, read_source, source_samples  # noqa: E402,F401
+
+
+FRAME_SECONDS = 0.02                # one model output step (codes.align.ForcedAligner.frame_to_seconds)
 
 
 def normalised_transcript(path):
@@ -89,9 +111,11 @@ def path_terms(probs, states, labels, blank):
     return probs.gather(1, sym[:, None])[:, 0].log().double()
 
 
-def cut_at_segments(res, blocks, frames, terms):
+def cut_at_segments(res, blocks, frames, terms, gap=None):
     """The ``segments`` entries: ``res`` LongAligner's result over the concatenated frames, ``terms`` the path's per-frame
-    terms on the host (None without an alignment)."""
+    terms on the host (None without an alignment).  ``gap`` (--gap-penalty: the absorbed frames, (T,) bool on the host): every
+    entry gains ``gap_frames`` and its score is taken over the other frames; the ``gaps`` list is returned beside the
+    entries."""
     sec = ForcedAligner.frame_to_seconds
     first = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)               # F_k, and the total at the end
     owner = lambda t: int(np.searchsorted(first, t, side='right')) - 1              # noqa: E731
@@ -110,12 +134,22 @@ def cut_at_segments(res, blocks, frames, terms):
                 clean[k] = False
         words[owner(s)].append({'word': word, 'start': round(time_of(s), 3), 'end': round(time_of(e), 3)})
     out = []
+    gaps = []
     for k, n_k in enumerate(frames):
         spf = None if terms is None or n_k == 0 else float(terms[first[k]:first[k + 1]].sum()) / n_k
-        out.append({'start': round(int(blocks[k][0]) / 100.0, 3), 'end': round(int(blocks[k][1]) / 100.0, 3), 'frames': n_k,
-                    'text': ' '.join(w['word'] for w in words[k]), 'score_per_frame': spf, 'clean': clean[k],
-                    'words': words[k]})
-    return out
+        seg = {'start': round(int(blocks[k][0]) / 100.0, 3), 'end': round(int(blocks[k][1]) / 100.0, 3), 'frames': n_k,
+               'text': ' '.join(w['word'] for w in words[k]), 'score_per_frame': spf, 'clean': clean[k], 'words': words[k]}
+        if gap is not None:
+            g_k = gap[first[k]:first[k + 1]]
+            kept = n_k - int(g_k.sum())
+            seg['gap_frames'] = n_k - kept
+            seg['score_per_frame'] = (None if terms is None or kept == 0
+                                      else float(terms[first[k]:first[k + 1]][~g_k].sum()) / kept)
+            edges = np.flatnonzero(np.diff(np.concatenate([[0], g_k.astype(np.int8), [0]])))     # run starts and ends
+            gaps += [{'start': round(time_of(first[k] + a), 3), 'end': round(time_of(first[k] + b - 1), 3), 'segment': k}
+                     for a, b in zip(edges[::2], edges[1::2])]
+        out.append(seg)
+    return out if gap is None else (out, gaps)
 
 
 def align_samples(path, samples, labels, model, frontend, segmenter, aligner, batch_size, device='cuda'):
@@ -134,18 +168,28 @@ def align_samples(path, samples, labels, model, frontend, segmenter, aligner, ba
            'band_states': res['band_states'], 'band_margin': res['band_margin'],
            'noise_floor_db': None if stats['noise_floor_db'] is None else round(stats['noise_floor_db'], 2),
            'threshold_db': None if stats['threshold_db'] is None else round(stats['threshold_db'], 2),
-           'speech_seconds': round(stats['speech_seconds'], 3),
-           'segments': cut_at_segments(res if ok else {'chars': [], 'words': []}, blocks, frames, terms)}
+           'speech_seconds': round(stats['speech_seconds'], 3)}
+    cut = res if ok else {'chars': [], 'words': []}
+    if 'gap' not in res:
+        rec['segments'] = cut_at_segments(cut, blocks, frames, terms)
+        return rec, blocks
+    gap = res['gap'].cpu().numpy().astype(bool)
+    rec['segments'], gaps = cut_at_segments(cut, blocks, frames, terms, gap)
+    rec.update(gap_penalty=aligner.gap_penalty, gap_seconds=round(int(gap.sum()) * FRAME_SECONDS, 3),
+               band_recentred=res['band_recentred'], gaps=gaps)
     return rec, blocks
 
 
-def write_clips(rec, blocks, samples, audio_path, clips_dir, data_dir, threshold):
-    """The clips of one recording -> manifest rows."""
+def write_clips(rec, blocks, samples, audio_path, clips_dir, data_dir, threshold, max_gap_seconds=None):
+    """The clips of one recording -> manifest rows.  ``max_gap_seconds`` (--gap-penalty): a segment with more absorbed audio
+    than this is not written."""
     stem = os.path.splitext(os.path.basename(audio_path))[0]
     name = (lambda p: os.path.relpath(os.path.abspath(p), os.path.abspath(data_dir)) if data_dir else os.path.abspath(p))
     rows = []
     for k, seg in enumerate(rec['segments']):
         if not (seg['clean'] and seg['text'] and seg['score_per_frame'] is not None and seg['score_per_frame'] >= threshold):
+            continue
+        if max_gap_seconds is not None and seg['gap_frames'] * FRAME_SECONDS > max_gap_seconds:
             continue
         clip = np.asarray(samples[160 * int(blocks[k][0]):min(len(samples), 160 * int(blocks[k][1]))], dtype='<i2')
         wav_path = os.path.join(clips_dir, '%s_%05d.wav' % (stem, k))
@@ -176,6 +220,11 @@ def main(argv=None):
     p.add_argument('--band-states', default=4096, type=int, help='states per frame the alignment starts with (default: 4096)')
     p.add_argument('--band-margin', default=16, type=int,
                    help='the band is doubled while the path comes closer than this to its edge (default: 16)')
+    p.add_argument('--gap-penalty', default=None, type=float, metavar='G',
+                   help='let the blanks between words absorb audio the transcript does not cover, at G nats per absorbed frame '
+                        'below the frame\'s best symbol (default: off; a placeholder, nobody has measured a good value)')
+    p.add_argument('--max-gap-seconds', default=None, type=float, metavar='X',
+                   help='with --gap-penalty: a clip is written only if it holds at most X seconds of absorbed audio (default: 0)')
     p.add_argument('--clips-dir', default=None, type=str, help='write the clean segments at or above the threshold here')
     p.add_argument('--clips-manifest', default=None, type=str, help='the manifest (wav,txt,duration) of the written clips')
     p.add_argument('--min-score-per-frame', default=None, type=float,
@@ -195,6 +244,13 @@ def main(argv=None):
         p.error('--clips-dir, --clips-manifest and --min-score-per-frame go together')
     if args.batch_size < 1:
         p.error('--batch-size must be at least 1')
+    if args.max_gap_seconds is not None and args.gap_penalty is None:
+        p.error('--max-gap-seconds needs --gap-penalty')
+    if args.gap_penalty is not None and not args.gap_penalty >= 0:
+        p.error('--gap-penalty must not be negative')
+    if args.max_gap_seconds is not None and not args.max_gap_seconds >= 0:
+        p.error('--max-gap-seconds must not be negative')
+    max_gap = None if args.gap_penalty is None else (args.max_gap_seconds or 0.0)
     if args.band_states < 1 or args.band_margin < 0:
         p.error('--band-states must be positive and --band-margin not negative')
     if args.audio:
@@ -237,7 +293,8 @@ def main(argv=None):
     model, _, val_t, target_t = load_model(args.model_path, return_transforms=True, data_dir=args.data_dir, ckpt=ckpt)
     model.eval().to('cuda')
     target_t = target_t[0]
-    aligner = LongAligner(target_t.label_encoder, band_states=args.band_states, band_margin=args.band_margin)
+    aligner = LongAligner(target_t.label_encoder, band_states=args.band_states, band_margin=args.band_margin,
+                          gap_penalty=args.gap_penalty)
     frontend = BatchSpectrogram(device='cuda', scale=waveform_scale(val_t))
     resampler = Resample(SAMPLE_RATE, device='cuda') if args.resample else None
     if args.clips_dir is not None:
@@ -260,7 +317,8 @@ def main(argv=None):
             if args.clips_dir is not None and rec['score'] is not None:
                 if torch.is_tensor(samples):                # (--resample: the converted samples come back for the clips)
                     samples = samples.cpu().numpy()
-                clip_rows += write_clips(rec, blocks, samples, path, args.clips_dir, args.data_dir, args.min_score_per_frame)
+                clip_rows += write_clips(rec, blocks, samples, path, args.clips_dir, args.data_dir, args.min_score_per_frame,
+                                        max_gap)
     if args.clips_manifest is not None:
         with open(args.clips_manifest, 'w') as f:
             f.write(''.join(r + '\n' for r in clip_rows))

@@ -697,6 +697,36 @@ int ds2_ctc_align_banded(const float* probs, const int32_t* sizes, const int32_t
                          int blank, int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts,
                          int32_t* ends, double* score, void* stream);
 
+/* ------------------------------------------------------------------ banded CTC alignment with gaps (csrc/ctc_align_banded.hip)
+ * Not in the reference.  ds2_ctc_align_banded for recordings with stretches the transcript does not cover: the blank states
+ * BETWEEN WORDS may absorb a frame whatever the model says about it, at a fixed price below the frame's best symbol.
+ * Everything of ds2_ctc_align_banded holds -- the states S = 2 L + 1, their predecessors, the band and its rules, the virtual
+ * first row, the end states, the ties, the fp64 sums, "no alignment" -- except the emission of some blank states:
+ *   frame values  lp[t][a] is the fp32 term of the existing entry (the input, or its logf unless log_input; NaN counts as
+ *                 -inf).  m[t] = max_a lp[t][a], -inf if the row has nothing finite.  f[t] = m[t] - g, ONE fp32 subtraction,
+ *                 -inf when m[t] is -inf.  g = gap_penalty, fp32, >= 0; +inf is allowed.
+ *   eligibility   state s is eligible if it is a blank (s even) and s == 0, or s == 2 L, or labels[s/2 - 1] == space, or
+ *                 labels[s/2] == space.  With space = -1 only the two end blanks are eligible; an empty transcript's one
+ *                 state is eligible.
+ *   emission      at an eligible state e = f[t], and the frame is a GAP FRAME, if f[t] > lp[t][blank] (strict, in fp32);
+ *                 otherwise e = lp[t][blank].  Every other state's emission is unchanged.  The choice depends on (t, s)
+ *                 only, never on the path, so the maximum over predecessors and its tie rule are untouched.
+ *   outputs       states, starts, ends and the fp64 score as before; the score includes the gap frames' f[t].  gap (B,T)
+ *                 uint8: 1 where the returned path's frame is a gap frame, 0 elsewhere below sizes[b], 0 past sizes[b], all 0
+ *                 without an alignment.
+ *   identity      with g = +inf, states / starts / ends / score are ds2_ctc_align_banded's bit for bit and gap is all zero.
+ *                 With g = 0 every eligible state takes the frame's best symbol for free.
+ * space: the label id that separates words, or -1.  DS2_ERR_ARG before any launch: g negative or NaN; space outside
+ * {-1} u [0, A) or equal to blank; everything ds2_ctc_align_banded refuses.  ws >= ds2_ctc_align_banded_gap_ws_bytes(B, T,
+ * band) bytes (the gap flag is a spare bit of the back-pointer byte, so the size is the plain entry's); need not be zeroed.
+ * Results are bit-identical from run to run and depend neither on the batch's other utterances nor on the workspace's contents.
+ * Added without a change of DS2_ABI_VERSION: two new symbols, no existing signature altered. */
+size_t ds2_ctc_align_banded_gap_ws_bytes(int B, int T, int band);
+int ds2_ctc_align_banded_gap(const float* probs, const int32_t* sizes, const int32_t* labels, const int32_t* label_offsets,
+                             const int32_t* label_lens, const int32_t* lo, int B, int T, int A, int max_label_len, int band,
+                             int blank, int space, float gap_penalty, int log_input, void* ws, size_t ws_bytes,
+                             int32_t* states, int32_t* starts, int32_t* ends, uint8_t* gap, double* score, void* stream);
+
 /* ------------------------------------------------------------------ keyword search (csrc/ctc_keyword.hip)
  * Not in the reference, so every rule here is this project's decision.  For every utterance b of a batch and every one of K
  * keywords: where was the keyword said, and how far must the model leave its own best path to have said it there.  Each
