@@ -4,6 +4,8 @@
 // sequence flavour over the task's rows alone -- what the reference's per-head BatchNorm1d sees after x[:, b0:b1] -- with fp32
 // partials combined in fp64.  The normalised rows are written PACKED, task after task, as contiguous (T, B_g, F) blocks (each
 // head's FC is then one plain GEMM), and the backward reads the packed gradient and writes the interleaved (T,B,F) one.
+#include <limits.h>
+
 #include "ds2_common.h"
 
 namespace {
@@ -212,6 +214,9 @@ inline int seg_ew_blocks(size_t n) {
     return (int)b;
 }
 
+// the kernels index a task's rows (rows = T * B_g, r = R - T * b0) in int
+inline bool seg_rows_fit(int T, int B) { return (long long)T * B <= INT_MAX; }
+
 // bounds_host: G + 1 column offsets, 0 = b0[0] < b0[1] < ... < b0[G] = B
 bool seg_args(int G, const int* bounds_host, int B, SegArgs* sa) {
     if (G < 1 || G > SEG_MAX || !bounds_host || bounds_host[0] != 0 || bounds_host[G] != B) return false;
@@ -230,6 +235,7 @@ extern "C" int ds2_bn1d_seg_stats(const float* xa, const float* xb, int T, int B
                                   float eps, float momentum, int use_running, float* const* running_mean_host,
                                   float* const* running_var_host, float* mean_invstd, void* ws, void* stream) {
     DS2_CHECK_ARG(xa && mean_invstd && ws && T > 0 && B > 0 && F > 0);
+    DS2_CHECK_ARG(seg_rows_fit(T, B));
     SegArgs sa;
     DS2_CHECK_ARG(seg_args(G, bounds_host, B, &sa));
     DS2_CHECK_ARG(!use_running || (running_mean_host && running_var_host));
@@ -259,6 +265,7 @@ extern "C" int ds2_bn1d_seg_apply(const float* xa, const float* xb, const float*
                                   const int* bounds_host, const float* const* gamma_host, const float* const* beta_host,
                                   float* y, void* stream) {
     DS2_CHECK_ARG(xa && mean_invstd && gamma_host && beta_host && y && T > 0 && B > 0 && F > 0);
+    DS2_CHECK_ARG(seg_rows_fit(T, B));
     SegArgs sa;
     DS2_CHECK_ARG(seg_args(G, bounds_host, B, &sa));
     bool vec = (F & 3) == 0 && al16(xa) && al16(xb) && al16(y) && al16(mean_invstd);
@@ -284,6 +291,7 @@ extern "C" int ds2_bn1d_seg_bwd(const float* xa, const float* xb, const float* d
                                 float* const* dgamma_host, float* const* dbeta_host, void* ws, void* stream) {
     DS2_CHECK_ARG(xa && dxf && mean_invstd && gamma_host && dy && dgamma_host && dbeta_host && ws);
     DS2_CHECK_ARG(T > 0 && B > 0 && F > 0);
+    DS2_CHECK_ARG(seg_rows_fit(T, B));
     SegArgs sa;
     DS2_CHECK_ARG(seg_args(G, bounds_host, B, &sa));
     bool vec = (F & 3) == 0 && al16(xa) && al16(xb) && al16(dxf) && al16(dy) && al16(mean_invstd);

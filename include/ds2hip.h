@@ -370,7 +370,8 @@ int ds2_bn1d_bwd(const float* xa, const float* xb, const float* dy, const float*
  * reference's per-head BatchNorm1d on x[:, b0:b1].  The *_host arguments are host arrays of G device pointers.
  * mean_invstd: (G, 2F), task g's mean then invstd.  ws: >= G * ds2_bn_ws_bytes(F) bytes.
  * stats: training (use_running=0) updates each task's running_mean / running_var (both arrays may be NULL: no update);
- * use_running=1 reads them instead. */
+ * use_running=1 reads them instead.
+ * Limit: T * B <= INT_MAX (the kernels index rows in int); beyond it DS2_ERR_ARG, nothing is launched. */
 int ds2_bn1d_seg_stats(const float* xa, const float* xb, int T, int B, int F, int G, const int* bounds_host,
                        float eps, float momentum, int use_running, float* const* running_mean_host,
                        float* const* running_var_host, float* mean_invstd, void* ws, void* stream);
