@@ -2,7 +2,7 @@
 // work and workspace are T x W instead of T x (2 L + 1) -- an hour of audio against its whole transcript in one launch.
 //
 // One workgroup per utterance, ONE launch, no workgroup waits on another.  Everything that ctc_align.hip says about the
-// recursion, its fp64 scores, the per-frame term and the tie rule holds here; what differs:
+// recursion, its fp64 scores and the per-frame term holds here, and the shared parts are ctc_path_common.h's; what differs:
 //   band        at frame t the admissible states are lo[t] <= s < lo[t] + W (and s < S = 2 L + 1).  State s lives in SLOT
 //               s mod W of the score row and of the frame's W back-pointer bytes, so a band that slides moves no data: the
 //               slot of a state that leaves the band is taken over by the state W above it.  Thread tid owns the slots
@@ -20,7 +20,7 @@
 //   symbols     a thread keeps the symbol and the skip flag of each of its K states in registers and re-reads them from
 //               labels (L2-resident) only when the band's movement puts another state into that slot.
 //   score       float64: an hour's path score is about -1e5.
-// Score rows: 2 x W doubles of dynamic LDS (128 KiB at W = 8192; the static part is 17 KiB).  Back-trace as in ctc_align.hip.
+// Score rows: 2 x W doubles of dynamic LDS (128 KiB at W = 8192; the static part is 17 KiB).
 // Critical path: T barriers per utterance, then T dependent LDS reads of one thread.
 //
 // GAP = true is ds2_ctc_align_banded_gap (include/ds2hip.h, "banded CTC alignment with gaps"): the same states, band, scores
@@ -33,18 +33,13 @@
 //   gap flag    bit 2 of the back-pointer byte (code | gap << 2), written by the recursion; the back-trace steps by
 //               (byte & 3) and writes gap[t] from the byte of the state it walks through.
 // The GAP = false instantiations contain none of this.
-#include "ds2_common.h"
+#include "ctc_path_common.h"
 
 namespace {
 
+using namespace ctc_path;
+
 constexpr int BAND_MIN = DS2_ALIGN_BAND_MIN, BAND_MAX = DS2_ALIGN_BAND_MAX;
-constexpr int EM_FLOATS = 1024;          // per staging buffer: CH = min(32, 1024 / A) frames
-constexpr int EM_NLD = 4;                // staging loads per thread and chunk (threads 0..255 do the staging)
-constexpr int MAX_CH = 32;
-constexpr int MAX_A = 256;               // CH >= 4
-constexpr int BT_F = 64;                 // back-trace: frames per window
-constexpr int BT_W = 2 * BT_F;           // ... and states per window row (the walk needs 2 (BT_F - 1) + 1)
-#define NEG_INF_D (-(double)INFINITY)
 
 template <int W, int NTHR, int K, bool GAP>
 __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
@@ -58,77 +53,40 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
     __shared__ float em[2][EM_FLOATS];
     __shared__ int lo_s[2][MAX_CH];
     __shared__ float mrow[GAP ? 2 : 1][GAP ? MAX_CH : 1];   // GAP: f[t] = max_a lp[t][a] - gap_penalty of the staged frames
-    __shared__ uint8_t pgap[GAP ? BT_F : 1];                // GAP: the gap flag of the path's frames in a back-trace window
-    __shared__ uint8_t win[BT_F][BT_W];
-    __shared__ int path[BT_F + 2];       // path[1 + f] = state at frame t_lo + f; [0] / [n + 1] = the frames around the window
     __shared__ int bad;
 
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int Lraw = label_lens[b];
-    const bool len_ok = Lraw >= 0 && Lraw <= lmax;
-    const int L = len_ok ? Lraw : 0;
-    const int tl = min(max(sizes[b], 0), T);
-    const int S = 2 * L + 1;
-    if (tid == 0) bad = len_ok ? 0 : 1;
-    __syncthreads();
-    const int32_t* lab = labels + label_offsets[b];
-    for (int l = tid; l < L; l += NTHR) {
-        const int sym = lab[l];
-        if (sym < 0 || sym >= A || sym == blank) bad = 1;   // reported as infeasible, never used as an index
-    }
+    const int tid = threadIdx.x;
+    const AlignUtt u = align_prologue<NTHR, GAP>(sizes, labels, label_offsets, label_lens, T, A, lmax, blank, states, starts,
+                                                 ends, gap_all, bad);
+    const int tl = u.tl, S = u.S;
+    const int32_t* lab = u.lab;
     for (int i = tid; i < W; i += NTHR) {
-        rowbuf[i] = (i == 0) ? 0.0 : NEG_INF_D;             // the virtual row before frame 0
-        rowbuf[W + i] = NEG_INF_D;
+        rowbuf[i] = (i == 0) ? 0.0 : NEG_INF;               // the virtual row before frame 0
+        rowbuf[W + i] = NEG_INF;
     }
     __syncthreads();
 
-    int32_t* st_out = states + (size_t)b * T;
-    int32_t* start_out = starts + (size_t)b * lmax;
-    int32_t* end_out = ends + (size_t)b * lmax;
-    uint8_t* gap_out = GAP ? gap_all + (size_t)b * T : nullptr;
-    for (int t = tl + tid; t < T; t += NTHR) {
-        st_out[t] = -1;
-        if constexpr (GAP) gap_out[t] = 0;
-    }
-    for (int l = L + tid; l < lmax; l += NTHR) start_out[l] = end_out[l] = -1;
-
-    uint8_t* bp = bp_all + (size_t)b * T * W;
-    double final_v = NEG_INF_D;
+    uint8_t* bp = bp_all + (size_t)blockIdx.x * T * W;
+    double final_v = NEG_INF;
     int final_s = -1;
-    if (!bad && tl > 0) {
+    const bool ok = !bad;
+    if (ok && tl > 0) {
         int held[K], symskip[K];                            // the state each owned slot holds; its symbol | skip << 8 | eligible << 9
 #pragma unroll
         for (int k = 0; k < K; ++k) held[k] = -1, symskip[k] = 0;
-        // staging roles: thread tid < 256 carries elements idx = tid + 256 i of a chunk (CH frames of A floats, contiguous),
-        // thread tid < CH the chunk's lo[tid]
-        const int CH = min(MAX_CH, EM_FLOATS / A), nper = CH * A;
-        const int nchunk = (tl + CH - 1) / CH;
-        const float* pb = probs + (size_t)b * T * A;
-        const int32_t* lo_row = lo_all + (size_t)b * T;
-        float ra[EM_NLD];
+        // staging roles besides the stager's: thread tid < CH carries the chunk's lo[tid]
+        ChunkStager stage(probs + (size_t)blockIdx.x * T * A, tid, tl, A);
+        const int CH = stage.CH, nchunk = stage.nchunk;
+        const int32_t* lo_row = lo_all + (size_t)blockIdx.x * T;
         int rlo = 0;
+        const auto term = [&](float a, int) { return log_input ? a : logf(a); };   // log 0 = -inf, log of a negative = NaN
         auto stage_load = [&](int c) {
-            const int left = (tl - c * CH) * A;             // floats of valid frames from this chunk's start on
-#pragma unroll
-            for (int i = 0; i < EM_NLD; ++i) {
-                const int idx = tid + 256 * i;
-                ra[i] = 0.f;
-                if (tid < 256 && idx < nper && idx < left) ra[i] = pb[(size_t)c * nper + idx];
-            }
+            stage.load(c);
             rlo = 0;
             if (tid < CH && c * CH + tid < tl) rlo = lo_row[c * CH + tid];
         };
         auto stage_store = [&](int buf) {
-#pragma unroll
-            for (int i = 0; i < EM_NLD; ++i) {
-                const int idx = tid + 256 * i;
-                if (tid < 256 && idx < nper) {
-                    float a = ra[i];
-                    asm volatile("" : "+v"(a));             // keeps the wait for the loads HERE, at the chunk's last frame
-                    if (!log_input) a = logf(a);            // log 0 = -inf, log of a negative = NaN
-                    em[buf][idx] = (a == a) ? a : -INFINITY;
-                }
-            }
+            stage.store(em[buf], term);
             if (tid < CH) lo_s[buf][tid] = rlo;
         };
         stage_load(0);
@@ -193,10 +151,10 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                             gapf = ((symskip[k] >> 9) & 1) && fgap > ev;            // strict, in fp32
                             ev = gapf ? fgap : ev;
                         }
-                        const double x0 = (unsigned)d < (unsigned)W ? r0 : NEG_INF_D;
-                        const double x1 = (unsigned)(d - 1) < (unsigned)W ? r1 : NEG_INF_D;
-                        const double x2 = (((symskip[k] >> 8) & (GAP ? 1 : -1)) && (unsigned)(d - 2) < (unsigned)W) ? r2 : NEG_INF_D;
-                        double best = x0;
+                        const double x0 = (unsigned)d < (unsigned)W ? r0 : NEG_INF;
+                        const double x1 = (unsigned)(d - 1) < (unsigned)W ? r1 : NEG_INF;
+                        const double x2 = (((symskip[k] >> 8) & (GAP ? 1 : -1)) && (unsigned)(d - 2) < (unsigned)W) ? r2 : NEG_INF;
+                        double best = x0;                   // the tie rule, written out: profiles/align_refactor.md, "Time"
                         int code = 0;
                         if (x1 > best) {
                             best = x1;
@@ -206,7 +164,7 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                             best = x2;
                             code = 2;
                         }
-                        nxt[j] = (best == NEG_INF_D) ? NEG_INF_D : best + (double)ev;
+                        nxt[j] = (best == NEG_INF) ? NEG_INF : best + (double)ev;
                         bp[(size_t)t * W + j] = (uint8_t)(GAP ? code | (gapf << 2) : code);
                     }
                 }
@@ -230,61 +188,12 @@ __global__ __launch_bounds__(NTHR) void ctc_align_banded_kernel(
                 final_s = S - 2;
             }
         }
-    } else if (!bad && tl == 0 && L == 0) {
-        final_v = 0.0;                                      // the empty path of an empty transcript
     }
-    if (tid == 0) score[b] = final_v == final_v ? final_v : NEG_INF_D;
-    const bool feasible = final_v != NEG_INF_D && final_v == final_v;
-    if (!feasible || tl == 0) {
-        for (int t = tid; t < tl; t += NTHR) {
-            st_out[t] = -1;
-            if constexpr (GAP) gap_out[t] = 0;
-        }
-        for (int l = tid; l < L; l += NTHR) start_out[l] = end_out[l] = -1;
-        return;
-    }
-
-    // ---- back-trace: the pointer bytes were written by this workgroup's own waves.  A state on the path is in its frame's
-    // band, so its byte is the one in slot (state mod W) of that frame; the window's other bytes are never walked.
-    __threadfence();
-    __syncthreads();
-    int s_hi = final_s, after = -2;                         // state at frame t_hi - 1; state at frame t_hi (-2: none)
-    for (int t_hi = tl; t_hi > 0; t_hi -= BT_F) {
-        const int t_lo = max(0, t_hi - BT_F), n = t_hi - t_lo;
-        const int s_lo = max(0, s_hi - (BT_W - 1));
-        for (int idx = tid; idx < n * BT_W; idx += NTHR) {
-            const int f = idx / BT_W, col = s_lo + (idx % BT_W);
-            win[f][idx % BT_W] = (col <= s_hi) ? bp[(size_t)(t_lo + f) * W + (col & (W - 1))] : (uint8_t)0;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int w = s_hi;
-            path[n + 1] = after;
-            for (int f = n - 1; f >= 0; --f) {
-                path[1 + f] = w;
-                int code = win[f][max(w - s_lo, 0)];        // (w >= s_hi - 2 (n - 1 - f) >= s_lo on a path; the clamp is for the index only)
-                if constexpr (GAP) {
-                    pgap[f] = (uint8_t)((code >> 2) & 1);
-                    code &= 3;
-                }
-                w = max(w - min(code, 2), 0);               // the step below row 0 may leave the window: it is the next one's top
-            }
-            path[0] = t_lo > 0 ? w : -2;
-        }
-        __syncthreads();
-        for (int f = tid; f < n; f += NTHR) {
-            const int w = path[1 + f], t = t_lo + f;
-            st_out[t] = w;
-            if constexpr (GAP) gap_out[t] = pgap[f];
-            if (w & 1) {
-                if (path[f] != w) start_out[w >> 1] = t;
-                if (path[2 + f] != w) end_out[w >> 1] = t;
-            }
-        }
-        after = path[1];
-        s_hi = path[0];
-        __syncthreads();
-    }
+    const bool has_path = align_has_path<NTHR, GAP>(u, ok, final_v);
+    if (tid == 0) score[blockIdx.x] = final_v == final_v ? final_v : NEG_INF;
+    // A state on the path is in its frame's band, so its byte is the one in slot (state mod W) of that frame; the window's other
+    // bytes are never walked.
+    if (has_path) align_backtrace<NTHR, GAP>(u, bp, W, W - 1, final_s);
 }
 
 template <int W, int NTHR, int K, bool GAP>
@@ -311,13 +220,6 @@ int run(const char* fn, const float* probs, const int32_t* sizes, const int32_t*
         const int32_t* label_lens, const int32_t* lo, int B, int T, int A, int max_label_len, int band, int blank, int space,
         float gap_penalty, int log_input, void* ws, size_t ws_bytes, int32_t* states, int32_t* starts, int32_t* ends,
         uint8_t* gap, double* score, void* stream) {
-#define BANDED_CHECK_ARG(cond)                                      /* DS2_CHECK_ARG under the entry point's name */ \
-    do {                                                                                                            \
-        if (!(cond)) {                                                                                              \
-            ds2_set_error("%s: bad argument: %s", fn, #cond);                                                       \
-            return DS2_ERR_ARG;                                                                                     \
-        }                                                                                                           \
-    } while (0)
     if (band < BAND_MIN || band > BAND_MAX || (band & (band - 1)) != 0) {
         ds2_set_error("%s: band %d is not a power of two in %d..%d", fn, band, BAND_MIN, BAND_MAX);
         return DS2_ERR_ARG;
@@ -327,29 +229,10 @@ int run(const char* fn, const float* probs, const int32_t* sizes, const int32_t*
                       (INT32_MAX - 1) / 2);
         return DS2_ERR_ARG;
     }
-    if (A < 1 || A > MAX_A) {
-        ds2_set_error("%s: alphabet size %d is outside 1..%d", fn, A, MAX_A);
-        return DS2_ERR_ARG;
-    }
-    BANDED_CHECK_ARG(B >= 0 && T >= 0 && blank >= 0 && blank < A);
-    if (GAP && !(gap_penalty >= 0.f)) {                     // (a NaN fails the comparison)
-        ds2_set_error("%s: gap_penalty %g is negative or NaN", fn, (double)gap_penalty);
-        return DS2_ERR_ARG;
-    }
-    if (GAP && (space < -1 || space >= A || space == blank)) {
-        ds2_set_error("%s: space %d is neither -1 nor a symbol of 0..%d other than blank %d", fn, space, A - 1, blank);
-        return DS2_ERR_ARG;
-    }
-    if (B == 0) return DS2_OK;
-    // (labels may be NULL when every transcript is empty: it is read only below a positive label_lens[b])
-    BANDED_CHECK_ARG(sizes && label_offsets && label_lens && score && (probs || T == 0) && (lo || T == 0));
-    BANDED_CHECK_ARG((states || T == 0) && ((starts && ends) || max_label_len == 0) && (!GAP || gap || T == 0));
-    if (ws_bytes < ds2_ctc_align_banded_ws_bytes(B, T, band) || !ws) {
-        ds2_set_error("%s: workspace of %zu bytes < %s_ws_bytes = %zu", fn, ws_bytes, fn,
-                      ds2_ctc_align_banded_ws_bytes(B, T, band));
-        return DS2_ERR_ARG;
-    }
-    int rc = DS2_OK;
+    int rc = check_align_args(fn, true, GAP, probs, sizes, label_offsets, label_lens, lo, B, T, A, max_label_len, blank, space,
+                              gap_penalty, ws, ws_bytes, ds2_ctc_align_banded_ws_bytes(B, T, band), states, starts, ends, gap,
+                              score);
+    if (rc != DS2_OK || B == 0) return rc;
 #define DS2_BANDED(W_, N_, K_)                                                                                         \
     rc = launch<W_, N_, K_, GAP>(fn, B, (hipStream_t)stream, probs, sizes, labels, label_offsets, label_lens, lo, T, A, \
                                  max_label_len, blank, log_input, (uint8_t*)ws, states, starts, ends, score, space,    \
@@ -365,7 +248,6 @@ int run(const char* fn, const float* probs, const int32_t* sizes, const int32_t*
         default: DS2_BANDED(8192, 1024, 8); break;
     }
 #undef DS2_BANDED
-#undef BANDED_CHECK_ARG
     if (rc != DS2_OK) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

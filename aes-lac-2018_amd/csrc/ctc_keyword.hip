@@ -11,24 +11,23 @@
 //               tie -- which with "stay first" is the contract's order stay, s-1, s-2.  The blank's predecessors are its own
 //               lane's.  Lane 0 takes the fresh start (0, t) instead.  No barrier and no LDS row per frame.
 //               The 4 waves of a workgroup take 4 keywords of the SAME utterance and share its normalised emissions
-//               e = logp - m, staged through LDS a chunk of frames at a time and loaded a chunk ahead as in ctc_align.hip:
+//               e = logp - m, staged through LDS a chunk of frames at a time and loaded a chunk ahead (ctc_path_common.h):
 //               one barrier per chunk.  Lane L - 1 owns D[t] and st[t] and runs the clustering pass on them in registers.
 // Critical path: T dependent steps of one wave (shuffle, compare, fp64 add); all pairs run side by side.
 // No workgroup waits on another; no atomics; outputs leave through ordinary vector stores.
-#include "ds2_common.h"
+#include "ctc_path_common.h"
 
 #include <limits.h>
 
 namespace {
 
+using namespace ctc_path;
+
 constexpr int KW_MAX_LEN = 64;           // DS2_KWS_MAX_LEN: one label per lane
 constexpr int KW_MAX_HITS = 64;
 constexpr int KW_WAVES = 4;              // keywords per workgroup
 constexpr int KW_NTHR = 64 * KW_WAVES;
-constexpr int EM_FLOATS = 1024;          // per staging buffer: CH = min(32, 1024 / A) frames
-constexpr int EM_NLD = EM_FLOATS / KW_NTHR;
-constexpr int MAX_A = 256;               // CH >= 4
-#define NEG_INF_D (-(double)INFINITY)
+static_assert(KW_NTHR == 256, "every thread stages");
 
 inline size_t rowmax_bytes(int B, int T) { return (((size_t)B * T * sizeof(float)) + 15) & ~(size_t)15; }
 
@@ -90,53 +89,33 @@ __global__ __launch_bounds__(KW_NTHR) void ctc_keyword_kernel(
     const int last = ok ? L - 1 : 0;                        // the lane of state S - 1
     const int sym_next = __shfl_down(sym, 1, 64);
     const bool skip_next = lane + 1 < L && sym_next != sym; // lane + 1's label may be entered from this lane's label
-    double thr = ok ? min_score[k] : NEG_INF_D;
+    double thr = ok ? min_score[k] : NEG_INF;
     asm volatile("" : "+v"(thr));                           // waited for HERE: inside the frame loop it would wait for the staging loads too
 
     const size_t pair = (size_t)b * K + (k < K ? k : 0);
     int32_t* hit_out = hits + pair * max_hits * 2;
     double* score_out = hit_score + pair * max_hits;
 
-    // ---- staging: thread tid carries elements idx = tid + 256 i of a chunk (CH frames of A floats, contiguous)
-    const int CH = min(32, EM_FLOATS / A), nper = CH * A;
-    const int nchunk = (tl + CH - 1) / CH;
-    const float* pb = logp + (size_t)b * T * A;
+    // ---- staging: with each float its frame's row maximum
+    ChunkStager stage(logp + (size_t)b * T * A, tid, tl, A);
+    const int CH = stage.CH, nchunk = stage.nchunk;
     const float* mb = rowmax + (size_t)b * T;
-    float ra[EM_NLD], rm[EM_NLD];
+    float rm[EM_NLD];
     int fr[EM_NLD];
 #pragma unroll
     for (int i = 0; i < EM_NLD; ++i) fr[i] = (tid + KW_NTHR * i) / A;
     auto stage_load = [&](int c) {
-        const int left = (tl - c * CH) * A;                 // floats of valid frames from this chunk's start on
 #pragma unroll
-        for (int i = 0; i < EM_NLD; ++i) {
-            const int idx = tid + KW_NTHR * i;
-            ra[i] = 0.f;
-            rm[i] = 0.f;
-            if (idx < nper && idx < left) {
-                ra[i] = pb[(size_t)c * nper + idx];
-                rm[i] = mb[c * CH + fr[i]];
-            }
-        }
+        for (int i = 0; i < EM_NLD; ++i) rm[i] = 0.f;
+        stage.load(c, [&](int i) { rm[i] = mb[c * CH + fr[i]]; });
     };
-    auto stage_store = [&](float* dst) {
-#pragma unroll
-        for (int i = 0; i < EM_NLD; ++i) {
-            const int idx = tid + KW_NTHR * i;
-            if (idx < nper) {
-                float a = ra[i];
-                asm volatile("" : "+v"(a));                 // keeps the wait for the loads HERE, after the chunk's frames
-                a = (a == a) ? a : -INFINITY;
-                const float e = a - rm[i];                  // the one fp32 subtraction; -inf - -inf and inf - inf are NaN
-                dst[idx] = (e == e) ? e : -INFINITY;
-            }
-        }
-    };
+    // the one fp32 subtraction; -inf - -inf and inf - inf are NaN
+    const auto term = [&](float a, int i) { return ((a == a) ? a : -INFINITY) - rm[i]; };
 
-    double v_lab = NEG_INF_D, v_blk = NEG_INF_D;
+    double v_lab = NEG_INF, v_blk = NEG_INF;
     int st_lab = -1, st_blk = -1;
     bool have = false;                                      // the current hit of the clustering pass (lane `last` only)
-    double h_score = NEG_INF_D;
+    double h_score = NEG_INF;
     int h_start = -1, h_end = -1, count = 0;
     auto emit = [&]() {
         if (count < max_hits) {
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(KW_NTHR) void ctc_keyword_kernel(
     };
 
     stage_load(0);
-    stage_store(em[0]);
+    stage.store(em[0], term);
     __syncthreads();
     int t = 0;
     for (int c = 0; c < nchunk; ++c) {
@@ -205,7 +184,7 @@ __global__ __launch_bounds__(KW_NTHR) void ctc_keyword_kernel(
                 }
             }
         }
-        if (more) stage_store(em[(c + 1) & 1]);             // (its last readers passed chunk c - 1's final barrier)
+        if (more) stage.store(em[(c + 1) & 1], term);       // after the chunk's frames (its last readers passed chunk c - 1's final barrier)
         __syncthreads();
     }
     if (lane == last && have) emit();
@@ -217,7 +196,7 @@ __global__ __launch_bounds__(KW_NTHR) void ctc_keyword_kernel(
         const bool hit = r < total;
         hit_out[2 * r] = hit ? hit_buf[wave][r][0] : -1;
         hit_out[2 * r + 1] = hit ? hit_buf[wave][r][1] : -1;
-        score_out[r] = hit ? score_buf[wave][r] : NEG_INF_D;
+        score_out[r] = hit ? score_buf[wave][r] : NEG_INF;
     }
 }
 
@@ -232,10 +211,7 @@ extern "C" int ds2_ctc_keyword_search(const float* logp, const int32_t* sizes, c
                                       const int32_t* label_offsets, const int32_t* label_lens, const double* min_score,
                                       int B, int T, int A, int K, int blank, int max_hits, void* ws, size_t ws_bytes,
                                       int32_t* hits, double* hit_score, int32_t* n_hits, void* stream) {
-    if (A < 1 || A > MAX_A) {
-        ds2_set_error("ds2_ctc_keyword_search: alphabet size %d is outside 1..%d", A, MAX_A);
-        return DS2_ERR_ARG;
-    }
+    if (check_alphabet(__func__, A) != DS2_OK) return DS2_ERR_ARG;
     if (K < 1 || K > 65535) {
         ds2_set_error("ds2_ctc_keyword_search: %d keywords is outside 1..65535", K);
         return DS2_ERR_ARG;
@@ -250,11 +226,7 @@ extern "C" int ds2_ctc_keyword_search(const float* logp, const int32_t* sizes, c
     if (B == 0) return DS2_OK;
     DS2_CHECK_ARG(sizes && labels && label_offsets && label_lens && min_score && hits && hit_score && n_hits);
     DS2_CHECK_ARG(logp || T == 0);
-    if (ws_bytes < ds2_ctc_keyword_search_ws_bytes(B, T) || !ws) {
-        ds2_set_error("ds2_ctc_keyword_search: workspace of %zu bytes < ds2_ctc_keyword_search_ws_bytes = %zu", ws_bytes,
-                      ds2_ctc_keyword_search_ws_bytes(B, T));
-        return DS2_ERR_ARG;
-    }
+    if (check_workspace(__func__, ws, ws_bytes, ds2_ctc_keyword_search_ws_bytes(B, T)) != DS2_OK) return DS2_ERR_ARG;
     float* rowmax = (float*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
     if (T > 0) {
         int G = 1;

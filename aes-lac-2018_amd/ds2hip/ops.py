@@ -1198,24 +1198,37 @@ def edit_stats(hyp, hyp_len, ref, ref_offsets, ref_lens, max_ref_len, space_id=-
     return stats
 
 
+def _align_call(entry, ws_arg, probs, head, max_label_len, tail, score_dtype, lo_name=None, with_gap=False):
+    """The call all three alignment wrappers make: ``entry(probs, *head, B, T, A, max_label_len, *tail, <workspace>, states,
+    starts, ends, [gap,] score)`` with the workspace of ``<entry>_ws_bytes(B, T, ws_arg)``.  ``head``: the device tensors
+    behind probs; ``lo_name``: the wrapper's name where head ends in ``lo``, whose shape is checked under it; ``with_gap``:
+    the entry has the gap output.  Returns states, starts, ends, gap or None, score."""
+    for x in (probs,) + head:
+        if not x.is_cuda:
+            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
+    bsz, t, a = probs.shape
+    if lo_name and (head[-1].dtype != torch.int32 or tuple(head[-1].shape) != (bsz, t)):
+        raise RuntimeError('%s: lo must be int32 of shape (B,T) = (%d,%d)' % (lo_name, bsz, t))
+    max_label_len = int(max_label_len)
+    ws = _bytes_ws(max(lib.query(entry + '_ws_bytes', bsz, t, int(ws_arg)), 16), probs)
+    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
+    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
+    ends = torch.empty_like(starts)
+    gap = torch.empty((bsz, t), dtype=torch.uint8, device=probs.device) if with_gap else None
+    score = torch.empty((bsz,), dtype=score_dtype, device=probs.device)
+    lib.call(entry, probs, *head, bsz, t, a, max_label_len, *tail, ws, ws.numel() * ws.element_size(), states, starts, ends,
+             *((gap,) if with_gap else ()), score)
+    return states, starts, ends, gap, score
+
+
 def ctc_align(probs, sizes, labels, label_offsets, label_lens, max_label_len, blank=0, log_input=False):
     """CTC forced alignment of a batch in one launch on the current stream (``ds2_ctc_align``).  probs (B,T,A) fp32 on the
     device; sizes (B,), flat labels, label_offsets (B,), label_lens (B,) int32 on the device.  Returns the device tensors
     states (B,T), starts, ends (B,max_label_len) int32 and score (B,) fp32; an utterance without an alignment has
     score -inf and -1 everywhere."""
-    for x in (probs, sizes, labels, label_offsets, label_lens):
-        if not x.is_cuda:
-            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
-    bsz, t, a = probs.shape
-    max_label_len = int(max_label_len)
-    ws_bytes = lib.query('ds2_ctc_align_ws_bytes', bsz, t, max_label_len)
-    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
-    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
-    ends = torch.empty_like(starts)
-    score = _empty((bsz,), probs)
-    lib.call('ds2_ctc_align', probs, sizes, labels, label_offsets, label_lens, bsz, t, a, max_label_len, int(blank),
-             int(bool(log_input)), ws, ws.numel(), states, starts, ends, score)
+    states, starts, ends, _, score = _align_call('ds2_ctc_align', max_label_len, probs,
+                                                 (sizes, labels, label_offsets, label_lens), max_label_len,
+                                                 (int(blank), int(bool(log_input))), torch.float32)
     return states, starts, ends, score
 
 
@@ -1225,21 +1238,10 @@ def ctc_align_banded(probs, sizes, labels, label_offsets, label_lens, max_label_
     utterance's frames: frame t admits the states lo[b,t] <= s < lo[b,t] + band.  ``band`` a power of two in
     lib.ALIGN_BAND_MIN .. lib.ALIGN_BAND_MAX.  Returns states, starts, ends as ``ctc_align`` and score (B,) FLOAT64; an
     utterance without an alignment inside its band (or with a bad band) has score -inf and -1 everywhere."""
-    for x in (probs, sizes, labels, label_offsets, label_lens, lo):
-        if not x.is_cuda:
-            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
-    bsz, t, a = probs.shape
-    if lo.dtype != torch.int32 or tuple(lo.shape) != (bsz, t):
-        raise RuntimeError('ctc_align_banded: lo must be int32 of shape (B,T) = (%d,%d)' % (bsz, t))
-    max_label_len, band = int(max_label_len), int(band)
-    ws_bytes = lib.query('ds2_ctc_align_banded_ws_bytes', bsz, t, band)
-    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
-    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
-    ends = torch.empty_like(starts)
-    score = torch.empty((bsz,), dtype=torch.float64, device=probs.device)
-    lib.call('ds2_ctc_align_banded', probs, sizes, labels, label_offsets, label_lens, lo, bsz, t, a, max_label_len, band,
-             int(blank), int(bool(log_input)), ws, ws.numel(), states, starts, ends, score)
+    states, starts, ends, _, score = _align_call('ds2_ctc_align_banded', band, probs,
+                                                 (sizes, labels, label_offsets, label_lens, lo), max_label_len,
+                                                 (int(band), int(blank), int(bool(log_input))), torch.float64,
+                                                 lo_name='ctc_align_banded')
     return states, starts, ends, score
 
 
@@ -1250,23 +1252,9 @@ def ctc_align_banded_gap(probs, sizes, labels, label_offsets, label_lens, max_la
     frame's best symbol (``ds2_ctc_align_banded_gap``; include/ds2hip.h has the definition).  Arguments as
     ``ctc_align_banded``.  Returns the device tensors states, starts, ends, gap (B,T) uint8 -- 1 where the path's frame was
     absorbed -- and score (B,) FLOAT64.  Nothing waits on the stream."""
-    for x in (probs, sizes, labels, label_offsets, label_lens, lo):
-        if not x.is_cuda:
-            raise RuntimeError('ds2hip entry points take device tensors; got a CPU tensor')
-    bsz, t, a = probs.shape
-    if lo.dtype != torch.int32 or tuple(lo.shape) != (bsz, t):
-        raise RuntimeError('ctc_align_banded_gap: lo must be int32 of shape (B,T) = (%d,%d)' % (bsz, t))
-    max_label_len, band = int(max_label_len), int(band)
-    ws_bytes = lib.query('ds2_ctc_align_banded_gap_ws_bytes', bsz, t, band)
-    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=probs.device)
-    states = torch.empty((bsz, t), dtype=torch.int32, device=probs.device)
-    starts = torch.empty((bsz, max(max_label_len, 0)), dtype=torch.int32, device=probs.device)
-    ends = torch.empty_like(starts)
-    gap = torch.empty((bsz, t), dtype=torch.uint8, device=probs.device)
-    score = torch.empty((bsz,), dtype=torch.float64, device=probs.device)
-    lib.call('ds2_ctc_align_banded_gap', probs, sizes, labels, label_offsets, label_lens, lo, bsz, t, a, max_label_len, band,
-             int(blank), int(space), float(gap_penalty), int(bool(log_input)), ws, ws.numel(), states, starts, ends, gap, score)
-    return states, starts, ends, gap, score
+    return _align_call('ds2_ctc_align_banded_gap', band, probs, (sizes, labels, label_offsets, label_lens, lo), max_label_len,
+                       (int(band), int(blank), int(space), float(gap_penalty), int(bool(log_input))), torch.float64,
+                       lo_name='ctc_align_banded_gap', with_gap=True)
 
 
 def keyword_search(logp, sizes, labels, label_offsets, label_lens, min_score, max_hits=4, blank=0, ws=None):

@@ -144,6 +144,25 @@ def test_the_band_moves(a):
     assert feasible >= 4
 
 
+@pytest.mark.parametrize('t', [3, 4, 5, 9])
+def test_every_staging_slot_in_use(t):
+    """A = 256, the largest alphabet: a staging chunk is 4 frames of 256 floats, so every slot of the buffer and every load
+    of a staging thread is in use; frame counts below, at and above one chunk and just above two.  Bands that admit
+    everything, that climb with the path, and one that leaves the first states behind."""
+    rng = np.random.default_rng(256 + t)
+    a, w = 256, 64
+    lens = [0, min(t, 2), t // 2, t // 2]
+    labels = [_labels(rng, n, a) for n in lens]
+    x = _dyadic(rng, (len(lens), t, a))
+    x[1::2][rng.random(x[1::2].shape) < 0.05] = -np.inf             # -inf holes for rows 1 and 3
+    lo = np.zeros((len(lens), t), dtype=np.int64)
+    lo[2] = np.minimum(bref.staircase(t, (0, 1)), 2 * lens[2])
+    lo[3] = np.minimum(bref.staircase(t, (1, 2)), 2 * lens[3])
+    want = _check_exact(x, [t, t, t, t - 1], labels, lo, w, (a, t))
+    assert np.isfinite(want[3][0]) and np.isfinite(want[3][2])     # (no holes; row 2's band follows the path of one state per frame)
+    print('T=%d scores %s' % (t, want[3]))
+
+
 def _raised_blank(rng, t, a, side):
     x = _dyadic(rng, (t, a))
     half = slice(0, t // 2) if side == 'late' else slice(t // 2, t)

@@ -90,6 +90,21 @@ def test_exact_over_frame_counts(a):
     assert feasible >= 2 * len(FRAMES) - 2
 
 
+@pytest.mark.parametrize('t', [3, 4, 5, 9])
+def test_exact_with_every_staging_slot_in_use(t):
+    """A = 256, the largest alphabet: a staging chunk is 4 frames of 256 floats, so every slot of the buffer and every load
+    of a staging thread is in use; frame counts below, at and above one chunk and just above two.  B = 4 as in
+    ``test_exact_over_frame_counts``."""
+    a = 256
+    rng = np.random.default_rng(a + t)
+    lens = [0, 1, min(t, 2), int(rng.integers(0, t // 2 + 2))]
+    labels = [_labels(rng, n, a) for n in lens]
+    x = _dyadic(rng, (4, t, a))
+    x[1::2][rng.random(x[1::2].shape) < 0.05] = -np.inf            # -inf holes for the second and the last utterance
+    want = _check_exact(x, [t, t, t, t], labels, (a, t))
+    assert np.isfinite(want[3][0])                                  # without holes the empty transcript always aligns
+
+
 @pytest.mark.parametrize('n', [0, 1, 2, 127, 128, 255, 256, 511])
 def test_exact_at_the_tightest_frame_count(n):
     """L labels need L + repeats frames: exactly that many (one path), one more, one fewer (no alignment), and a looser
