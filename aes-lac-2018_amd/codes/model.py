@@ -134,6 +134,10 @@ class _DS2Function(torch.autograd.Function):
 # 15.66, 82 free (28 units) 15.57 -- the slower recurrence form wins because dW_ih of the layer above then hides beside it too.
 _BWD_SPARE_CUS = int(os.environ.get('DS2_GRU_BWD_SPARE', '82'))
 
+# Largest K = (T - 1) * B at which a layer's four dW_hh problems go out as ONE grouped launch; above it each problem gets a
+# launch of its own with its own split of K (the measurement is beside the branch in ``_backward_impl``).
+_DW_HH_GROUP_MAX_K = 32768
+
 
 class DeepSpeech(nn.Module):
     __version__ = '0.0.1'
@@ -575,7 +579,7 @@ class DeepSpeech(nn.Module):
                         # one grouped launch while K = rows is moderate (same-box A/B of the whole step: B = 10 +0.6 %,
                         # B = 32 (K up to 24 k) +0.6 %, B = 64 x 15 s (K = 47 k) -1.6 %: there one launch per problem, each
                         # with its own finer split of K, is faster)
-                        if k <= 32768:
+                        if k <= _DW_HH_GROUP_MAX_K:
                             ops.gemm_tn_group(group, hid, k, accumulate=prezeroed)
                         else:
                             for a_p, lda, m_p, b_p, ldb, c_p, ldc in group:
